@@ -21,9 +21,18 @@ must equal --gpus.  `MH_DIST_BACKEND=gloo` rehearses the plan with several ranks
 
 Prints one JSON line (rank 0).  `roofline` is for the emission writer (k_emit_tiles): algorithmic bytes per launch =
 sum over kept templates of 2*rlen (haplotype bases gathered) + FASTQ bytes written (both files), divided by the
-launch's HIP-event duration on the writer's stream; `stage_ms` gives every stage per step.  At N = 1 the line also
-carries `cpu_baseline` (the CPU oracle on the host cores, and the configs[0] CPU config beside it) and `end_to_end`
-(the whole `generate-reads` command on chr1: files in, FASTQ to /dev/null).
+launch's HIP-event duration on the writer's stream; `stage_ms` gives every stage per step (both read from the timed
+steps' own HIP events: no run of their own).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` (N = 1) adds the legs that take runs of
+their own: `cpu_baseline` (the CPU oracle on the host cores, and the configs[0] CPU config beside it) and
+`end_to_end` (the whole `generate-reads` command on chr1: files in, FASTQ to /dev/null); `--no-cpu-baseline`,
+`--no-e2e` and the other leg flags trim it.  `--verify` (the full-size byte check) is asked for by name.
+
+`--dump-outputs DIR` (one GPU) writes what the last timed step computed as float64 / float32 `.npy` files: every
+unit's (templates drawn, templates kept, FASTQ bytes of file 1, of file 2), and a fixed, seeded sample of the FASTQ
+bytes that the step left in the device arenas (dump_outputs).  The inputs are seed-fixed, so two builds run with the
+same arguments can be compared file for file.
 """
 import argparse
 import collections
@@ -55,6 +64,12 @@ def parse():
   # (the first bench process on a fresh box ran 13 % slow with 2 warm-up steps in three calls, and at the rate of the
   # later processes with 40: profiles/r04/firstrun/)
   ap.add_argument('--warmup', type=int, default=30)
+  ap.add_argument('--full', action='store_true',
+                  help='N = 1: after the timed steps, also the legs that take runs of their own (the CPU baselines and '
+                       'the end-to-end command; --no-cpu-baseline, --no-e2e and the other leg flags trim them); a '
+                       'plain run times its steps and prints the line')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='one GPU, wgs or chr1: write what the last timed step computed to DIR/<name>.npy (dump_outputs)')
   ap.add_argument('--model', default='hiseq-X-v2.5-Garvan')
   ap.add_argument('--coverage', type=float, default=30.0)
   ap.add_argument('--length', type=int, default=CHR1)
@@ -73,10 +88,10 @@ def parse():
   ap.add_argument('--verify', action='store_true',
                   help='wgs, N = 1: after the timed steps, run one more step unit by unit and compare every unit\'s '
                        'FASTQ bytes (sha256 of its arena range, both files) with the CPU oracle\'s digests')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline legs')
   ap.add_argument('--no-prime', action='store_true',
                   help='skip the HBM first-touch pass (scripts/prime_hbm.py) run before the GPU is used')
-  ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end (files in, /dev/null out) leg')
+  ap.add_argument('--no-e2e', action='store_true', help='--full: skip the end-to-end (files in, /dev/null out) leg')
   ap.add_argument('--e2e-gz', action=argparse.BooleanOptionalAction, default=True,
                   help='end-to-end leg: also with BGZF-compressed output (host deflate, level 1)')
   ap.add_argument('--stages', action='store_true', help='print per-stage timings to stderr')
@@ -200,6 +215,7 @@ class LazyCounts:
   def __init__(self, eng):
     self.eng = eng
     self.q = collections.deque()
+    self.last = []   # [(n, kept, bytes1, bytes2)] per unit of the step read last (--dump-outputs)
 
   def getter(self, n):
     memo = []
@@ -209,9 +225,41 @@ class LazyCounts:
         while len(self.q) < n:
           self.q.extend(self.eng.collect())
         res = [self.q.popleft() for _ in range(n)]
+        self.last = res
         memo.append((sum(r[1] for r in res), sum(r[2] for r in res), sum(r[3] for r in res)))
       return memo[0]
     return get
+
+
+DUMP_CHUNKS, DUMP_CHUNK = 64, 1 << 16
+
+
+def dump_outputs(path, eng, rows):
+  """--dump-outputs: what a caller of the timed path holds after the last timed step, as .npy files under `path`.
+  unit_counts.npy (float64, units x 4): every unit's (templates drawn, templates kept, FASTQ bytes of file 1, of
+  file 2), in the step's queue order.  fastq1_sample.npy / fastq2_sample.npy (float32, DUMP_CHUNKS x DUMP_CHUNK, one
+  byte per element, zero past a short arena's end): the FASTQ bytes the step left in the device arenas (its last
+  batch; earlier batches' bytes were recycled) at the chunk offsets in fastq_sample_offsets.npy (float64,
+  DUMP_CHUNKS x 2) — the arena's head and tail and DUMP_CHUNKS - 2 offsets drawn from a fixed seed, scaled by the
+  arena's size.  34 MB in all.  Call before anything else resets the arenas."""
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  np.save(os.path.join(path, 'unit_counts.npy'), np.asarray(rows, dtype=np.float64).reshape(len(rows), 4))
+  eng.ctx.sync()
+  used = eng.ctx.output_size()
+  u = np.random.default_rng(20240607).random(DUMP_CHUNKS)
+  u[0], u[-1] = 0.0, 1.0
+  offs = np.zeros((DUMP_CHUNKS, 2), np.int64)
+  samples = [np.zeros((DUMP_CHUNKS, DUMP_CHUNK), np.float32) for _ in (0, 1)]
+  for k in range(DUMP_CHUNKS):
+    offs[k] = [int(u[k] * max(0, used[f] - DUMP_CHUNK)) for f in (0, 1)]
+    lens = [max(0, min(DUMP_CHUNK, used[f] - offs[k, f])) for f in (0, 1)]
+    got = eng.ctx.fetch_output_arrays(int(offs[k, 0]), lens[0], int(offs[k, 1]), lens[1])
+    for f in (0, 1):
+      samples[f][k, :lens[f]] = got[f]
+  np.save(os.path.join(path, 'fastq_sample_offsets.npy'), offs.astype(np.float64))
+  for f in (0, 1):
+    np.save(os.path.join(path, 'fastq{}_sample.npy'.format(f + 1)), samples[f])
 
 
 def timed(step, steps, warmup, eng, dist):
@@ -276,6 +324,8 @@ def launch_ranks(n):
 
 def main():
   a = parse()
+  if a.steps < 1 or a.warmup < 0:
+    sys.exit('bench.py: --steps counts the timed steps (at least 1), --warmup the untimed ones before them')
   ws = os.environ.get('WORLD_SIZE')
   if ws is None and a.gpus > 1:
     sys.exit(launch_ranks(a.gpus))
@@ -284,6 +334,8 @@ def main():
     sys.exit('bench.py: --gpus {} but WORLD_SIZE={}: the launcher and the flag disagree'.format(a.gpus, world))
   rank = int(os.environ.get('RANK', '0'))
   local = int(os.environ.get('LOCAL_RANK', '0'))
+  if a.dump_outputs and (world != 1 or a.tumor_normal):
+    sys.exit('bench.py: --dump-outputs is for one GPU and the wgs or chr1 workload')
   global PRIME_S
   a.prime_s = PRIME_S = prime_hbm(a, local)
   if a.tumor_normal and world > 1:
@@ -356,6 +408,8 @@ def run_chr1(a):
     return counts.getter(len(units))
 
   dt, kept, b1, b2, stages = timed(step, a.steps, a.warmup, eng, None)
+  if a.dump_outputs:
+    dump_outputs(a.dump_outputs, eng, counts.last)
   eng.close()
   roof, stage_ms, span_ms = roofline(stages, kept, b1, b2, rlen, kernel, a.steps,
                                      'chr1_corrupt' if a.corrupt else 'chr1')
@@ -366,10 +420,10 @@ def run_chr1(a):
     corrupt_pass = corrupt_roofline(stages, kept, b1, b2, rlen)
 
   e2e = None
-  if not a.no_e2e and not a.corrupt and a.rng == 'mitty':
+  if a.full and not a.no_e2e and not a.corrupt and a.rng == 'mitty':
     e2e = end_to_end(a, seq, recs, model, kept // a.steps)
   cpu = None
-  if not a.no_cpu_baseline and a.cpu_baseline_mbp > 0:
+  if a.full and not a.no_cpu_baseline and a.cpu_baseline_mbp > 0:
     cpu = cpu_baseline(a, seq, recs, p, rlen, model, units)
 
   ms_per_step = dt / a.steps * 1e3
@@ -819,6 +873,8 @@ def run_genome(a, rank, world, local):
 
   steps, warmup = a.steps, a.warmup
   dt, kept, b1, b2, stages = timed(step, steps, warmup, eng, dist)
+  if a.dump_outputs:
+    dump_outputs(a.dump_outputs, eng, lazy.last)
   verify = None
   if a.verify:
     if world != 1 or a.plan_share or a.rng != 'mitty':
@@ -839,7 +895,7 @@ def run_genome(a, rank, world, local):
   workload = 'wgs' if a.genome_scale == 1 else None
   roof, stage_ms, span_ms = roofline(stages, kept, b1, b2, rlen, kernel, steps, workload, world)
   cpu = e2e = None
-  if world == 1 and not a.plan_share:
+  if a.full and world == 1 and not a.plan_share:
     seq1, recs1, _ = data[0]
     if not a.no_e2e and a.genome_scale == 1 and a.rng == 'mitty':
       e2e = end_to_end(a, seq1, recs1, model, None)

@@ -5,7 +5,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/final_bench
 mkdir -p $O
-timeout -k 10 420 python -u bench.py > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 420 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit $?
 python3 scripts/bsum.py $O/bench.json || true
 python3 -c "
 import json; d = json.load(open('$O/bench.json')); e = d['end_to_end']

@@ -5,7 +5,9 @@ CPU oracle); the files the ranks pwrite together must equal the reference --thre
 for whole-unit LPT sharding and for sliced units (cnt bases from the all-reduced slice counts).
 """
 import os
+import sys
 
+import numpy as np
 import pytest
 
 from mitty_amd import distributed as D
@@ -157,6 +159,56 @@ def test_bench_batch_plan():
     assert len(b) >= min(mb, len(units))
     for x in b[:-1]:   # every batch but the last reaches its size
       assert sum(draws[u[1]] for u in x) >= size
+
+
+class _Arenas:
+  """Stands for Engine.ctx in bench.dump_outputs: two host arrays as the device arenas."""
+
+  def __init__(self, a1, a2):
+    self.a = (a1, a2)
+
+  def sync(self):
+    pass
+
+  def output_size(self):
+    return len(self.a[0]), len(self.a[1])
+
+  def fetch_output_arrays(self, off1, len1, off2, len2):
+    assert 0 <= off1 and off1 + len1 <= len(self.a[0]) and 0 <= off2 and off2 + len2 <= len(self.a[1])
+    return self.a[0][off1:off1 + len1], self.a[1][off2:off2 + len2]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+  """bench.py --dump-outputs: the per-unit counts as float64, the arenas sampled at the recorded offsets (head and
+  tail included) as float32, the same files for the same arenas, a short arena zero-padded; --full is off by
+  default."""
+  import types
+  import bench
+  monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'])
+  a = bench.parse()
+  assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+  rng = np.random.default_rng(5)
+  n = bench.DUMP_CHUNK
+  arenas = (rng.integers(0, 256, 5 * n + 17, dtype=np.uint8), rng.integers(0, 256, n // 2, dtype=np.uint8))
+  rows = [(1000 + k, 900 + k, 7 * k, 9 * k) for k in range(6)]
+  eng = types.SimpleNamespace(ctx=_Arenas(*arenas))
+  out = []
+  for d in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / d), eng, rows)
+    out.append({f: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+  assert sorted(out[0]) == ['fastq1_sample.npy', 'fastq2_sample.npy', 'fastq_sample_offsets.npy', 'unit_counts.npy']
+  for f in out[0]:
+    assert out[0][f].dtype in (np.float32, np.float64) and np.array_equal(out[0][f], out[1][f]), f
+  assert sum(x.nbytes for x in out[0].values()) <= 64e6
+  assert np.array_equal(out[0]['unit_counts.npy'], np.asarray(rows, np.float64))
+  offs = out[0]['fastq_sample_offsets.npy'].astype(np.int64)
+  assert offs.shape == (bench.DUMP_CHUNKS, 2)
+  assert offs[0, 0] == 0 and offs[-1, 0] == len(arenas[0]) - n and len(set(offs[:, 0].tolist())) > 8
+  assert not offs[:, 1].any()
+  for k in range(bench.DUMP_CHUNKS):
+    assert np.array_equal(out[0]['fastq1_sample.npy'][k], arenas[0][offs[k, 0]:offs[k, 0] + n].astype(np.float32))
+    assert np.array_equal(out[0]['fastq2_sample.npy'][k, :n // 2], arenas[1].astype(np.float32))
+    assert not out[0]['fastq2_sample.npy'][k, n // 2:].any()
 
 
 def _rank_few_units(rank, world, port, bed, outdir):
