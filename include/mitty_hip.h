@@ -22,6 +22,8 @@
  *   mh_corrupt_fastq      readcorrupt.multi_process's reader/worker/writer  mitty/simulation/readcorrupt.py:18-118
  *   mh_work_units         readgenerate.get_data_for_workers              mitty/simulation/readgenerate.py:129-159
  *   mh_read_model_params  illumina.read_model_params                     mitty/simulation/illumina.py:12-40
+ *   mh_bamfile_next       pysam.AlignmentFile.fetch                      mitty/benchmarking/mq.py:61-62
+ *   mh_score_add_records  mq / derr process_bam_part                     mitty/benchmarking/mq.py:50-68, derr.py:53-76
  *
  * Threading: one mh_ctx per GPU and per host thread; a context owns one HIP stream and all device buffers.
  * Calls are synchronous at return (device work is ordered on the context's stream; results copied back are
@@ -335,6 +337,59 @@ int32_t mh_bam_write_part(mh_ctx *ctx, const char *path, const char *header_text
                           int64_t *out_bytes, int64_t *boff, int64_t boff_cap);
 int32_t mh_bam_bai_runs(mh_ctx *ctx, int64_t *n_runs, int64_t *runs, int64_t runs_cap, int64_t *n_win, int64_t *win,
                         int64_t win_cap, int64_t *ref_nwin);
+
+/* ---- BAM reader (pysam.AlignmentFile + fetch of the scorers, mitty/benchmarking/mq.py:21,61-62, derr.py:20,65-66) --
+ * Host-only (no device): a BGZF BAM, sorted or not, no index.  Blocks are inflated on `threads` threads (the argument
+ * alone sizes the pool) and their CRC32 / ISIZE checked; the file is untrusted, so truncation, bad magic, a bad CRC, a
+ * record cut by the end of the file or one whose fields do not fit its block_size (l_read_name >= 1, NUL-terminated
+ * name, 32 + l_read_name + 4 n_cigar + (l_seq + 1) / 2 + l_seq <= block_size) are MH_E_ARG with a message in
+ * mh_bamfile_error.
+ *   mh_bamfile_header  header text (not NUL-terminated: text_len), n_ref, the names NUL-separated, the lengths;
+ *                      pointers valid until mh_bamfile_close
+ *   mh_bamfile_next    the next chunk of the record stream: whole records (each with its block_size) of about
+ *                      max_bytes bytes (at least one record), *n of them at recs + roff[i] (roff has n + 1 entries,
+ *                      roff[0] = 0, roff[n] = *len); *n = 0 at the end of the file.  Pointers valid until the next call.
+ *                      The chunk after it (same max_bytes) is inflated by a thread of the handle in the meantime, so
+ *                      the caller's work on one chunk overlaps the inflate of the next.  One thread uses a handle at
+ *                      a time.  mh_bamfile_header may be called whenever the open succeeded; mh_bamfile_error reads the
+ *                      message that thread may be writing, so call it only after a call on the handle has returned an
+ *                      error (the thread has been joined by then and none is started after a failure) */
+typedef struct mh_bamfile mh_bamfile;
+int32_t mh_bamfile_open(const char *path, int32_t threads, mh_bamfile **out);
+const char *mh_bamfile_error(const mh_bamfile *f);
+int32_t mh_bamfile_header(const mh_bamfile *f, const char **text, int64_t *text_len, int32_t *n_ref,
+                          const char **names, const int64_t **lengths);
+int32_t mh_bamfile_next(mh_bamfile *f, int64_t max_bytes, const uint8_t **recs, int64_t *len, const int64_t **roff,
+                        int64_t *n);
+int32_t mh_bamfile_close(mh_bamfile *f);
+
+/* ---- alignment scoring: mq-plot / derr-plot (mq.process_bam_part, mitty/benchmarking/mq.py:50-68;
+ * derr.process_bam_part, derr.py:53-76; readgenerate.parse_qname / score_alignment_error, readgenerate.py:259-319;
+ * cli.py:224-252).  One pass over BAM records on the device fills both matrices:
+ *   mq_mat    u64[100][2 max_d + 1]             mq_mat[mapq, d_err + max_d] += 1
+ *   derr_mat  u64[2 max_v + 2][2 max_d + 1]     per v of the read's v_list with 0 <= max_v + v < 2 max_v + 1 the row
+ *                                               max_v + v, for an empty v_list the last row; max_v = max(max_v_len, 51)
+ * Records with tid < 0 are not counted (the reference fetches per @SQ), then the sample-prefix filter
+ * (qname.startswith), then the group of the qname picked by flag 0x80.  strict: d_err = clamp(pos + 1 - ri.pos) on the
+ * qname's chrom, else max_d; otherwise the closest breakpoint ('=', 'M', 'X' ops of the qname CIGAR) strictly inside
+ * max_d, else max_d.  An unparseable qname, a read2 record on a one-group qname, MAPQ >= 100 and a tid past the names
+ * are MH_E_ARG naming the record (the reference raises); once a record fails nothing more is added.
+ *   mh_score_begin        a new session: header names (NUL-separated), sizes, mode, sample prefix (NULL: none)
+ *   mh_score_add_records  n records in host bytes at recs + roff[i] (n + 1 offsets, as mh_bamfile_next gives them), each
+ *                         checked as the reader checks them, staged in one of two page-locked buffers and queued:
+ *                         the call returns while the device works, so the next chunk inflates beside it; a failing
+ *                         record is reported by mh_score_result
+ *   mh_score_add_store    the context's own BAM record store (mh_bam_add_fastq / mh_bam_add_output) scored in HBM, no
+ *                         host round trip; reference names from mh_bam_set_refs
+ *   mh_score_result       waits; the matrices (either may be NULL) and counts[4] = records seen, scored, skipped for
+ *                         tid < 0, skipped by the sample filter
+ *   mh_score_reset        zero sums and no error, same session parameters */
+int32_t mh_score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_d, int32_t max_v_len,
+                       int32_t strict, const char *sample_prefix);
+int32_t mh_score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t mh_score_add_store(mh_ctx *ctx);
+int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
+int32_t mh_score_reset(mh_ctx *ctx);
 
 /* ---- VCF ingest (vcfio.load_variant_file / split_copies / parse, vcfio.py:51-126) ------
  * Host-only (no device): mh_vcf_open parses a plain or bgzipped VCF for one sample; mh_vcf_region runs the BED

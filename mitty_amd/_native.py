@@ -28,6 +28,8 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_output_bgzf_range', 'mh_output_bgzf_pair', 'mh_output_bgzf_wait', 'mh_output_fetch_async',
            'mh_output_fetch_wait',
            'mh_vcf_open', 'mh_vcf_error', 'mh_vcf_close', 'mh_vcf_region', 'mh_vcf_copy', 'mh_vcf_filter',
+           'mh_bamfile_open', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
+           'mh_score_begin', 'mh_score_add_records', 'mh_score_add_store', 'mh_score_result', 'mh_score_reset',
            'mh_fasta_open', 'mh_fasta_error', 'mh_fasta_count', 'mh_fasta_contig', 'mh_fasta_copy', 'mh_fasta_close']
 
 
@@ -139,6 +141,17 @@ def lib():
   _sig(L, 'mh_vcf_copy', [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_vcf_filter', [ctypes.c_char_p, ctypes.c_char_p, c_i32, c_vp, c_vp, c_vp, ctypes.c_char_p, c_i32, c_i32,
                             P_i64, P_i64, ctypes.c_char_p, c_i32])
+  _sig(L, 'mh_bamfile_open', [ctypes.c_char_p, c_i32, ctypes.POINTER(c_vp)])
+  _sig(L, 'mh_bamfile_error', [c_vp], ctypes.c_char_p)
+  _sig(L, 'mh_bamfile_header', [c_vp, ctypes.POINTER(c_vp), P_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
+                                ctypes.POINTER(c_vp)])
+  _sig(L, 'mh_bamfile_next', [c_vp, c_i64, ctypes.POINTER(c_vp), P_i64, ctypes.POINTER(c_vp), P_i64])
+  _sig(L, 'mh_bamfile_close', [c_vp])
+  _sig(L, 'mh_score_begin', [c_vp, c_i32, ctypes.c_char_p, c_i32, c_i32, c_i32, ctypes.c_char_p])
+  _sig(L, 'mh_score_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
+  _sig(L, 'mh_score_add_store', [c_vp])
+  _sig(L, 'mh_score_result', [c_vp, c_vp, c_vp, c_vp])
+  _sig(L, 'mh_score_reset', [c_vp])
   _sig(L, 'mh_fasta_open', [ctypes.c_char_p, c_vp, ctypes.POINTER(c_vp)])
   _sig(L, 'mh_fasta_error', [c_vp], ctypes.c_char_p)
   _sig(L, 'mh_fasta_count', [c_vp, ctypes.POINTER(c_i32)])
@@ -244,6 +257,63 @@ class VcfFile:
       copies.append({'pos': pos, 'op': op, 'oplen': oplen, 'alt_off': aoff, 'alt_len': alen,
                      'alt_pool': pool[:nb].tobytes()})
     return pl.value, copies
+
+
+class BamFile:
+  """Host BAM reader (mh_bamread.cpp): header fields, then chunks() of whole records.  `threads` sizes the inflate
+  pool."""
+
+  def __init__(self, path, threads=2):
+    L = lib()
+    self._L = L
+    self._h = c_vp()
+    rc = L.mh_bamfile_open(path.encode(), int(threads), ctypes.byref(self._h))
+    if rc:
+      msg = L.mh_bamfile_error(self._h).decode(errors='replace') if self._h else 'mh_bamfile_open failed'
+      self.close()
+      _raise(rc, msg)
+    text, names, lens = c_vp(), c_vp(), c_vp()
+    tl, n = c_i64(), c_i32()
+    L.mh_bamfile_header(self._h, ctypes.byref(text), ctypes.byref(tl), ctypes.byref(n), ctypes.byref(names),
+                        ctypes.byref(lens))
+    self.text = ctypes.string_at(text.value, tl.value).decode(errors='replace') if tl.value else ''
+    self.lengths = [int(x) for x in (c_i64 * n.value).from_address(lens.value)] if n.value else []
+    self.names, p = [], names.value
+    for _ in range(n.value):
+      s = ctypes.string_at(p)
+      self.names.append(s.decode(errors='replace'))
+      p += len(s) + 1
+    self.names_blob = ctypes.string_at(names.value, p - names.value) if n.value else b''
+
+  def close(self):
+    if getattr(self, '_h', None):
+      self._L.mh_bamfile_close(self._h)
+      self._h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def next_raw(self, max_bytes=64 << 20):
+    """(recs address, bytes, offsets address, records) of the next chunk, valid until the next call; records = 0 at
+    the end of the file."""
+    recs, roff = c_vp(), c_vp()
+    ln, n = c_i64(), c_i64()
+    rc = self._L.mh_bamfile_next(self._h, int(max_bytes), ctypes.byref(recs), ctypes.byref(ln), ctypes.byref(roff),
+                                 ctypes.byref(n))
+    if rc:
+      _raise(rc, self._L.mh_bamfile_error(self._h).decode(errors='replace'))
+    return recs.value, ln.value, roff.value, n.value
+
+  def chunks(self, max_bytes=64 << 20):
+    """Yields (record bytes, offsets int64[n + 1]) copies, chunk by chunk."""
+    while True:
+      recs, ln, roff, n = self.next_raw(max_bytes)
+      if n == 0:
+        return
+      yield ctypes.string_at(recs, ln), np.array((c_i64 * (n + 1)).from_address(roff), np.int64)
 
 
 def vcf_filter(path_in, sample, regions, path_out, bgzf=False, threads=8):
@@ -863,6 +933,41 @@ class Context:
 
   def bam_reset(self):
     self._chk(self._L.mh_bam_reset(self._h))
+
+  # ---- alignment scoring (mq-plot / derr-plot) ----
+  def score_begin(self, names, max_d=200, max_v_len=200, strict=False, sample_prefix=None):
+    """A new scoring session.  names: the BAM header's reference names (list, or the NUL-separated blob)."""
+    blob = names if isinstance(names, bytes) else b''.join(n.encode() + b'\0' for n in names)
+    n = blob.count(b'\0')
+    self._score_shape = (int(max_d), max(int(max_v_len), 51))
+    self._chk(self._L.mh_score_begin(self._h, n, blob if n else None, int(max_d), int(max_v_len), 1 if strict else 0,
+                                     sample_prefix.encode() if sample_prefix else None))
+
+  def score_add_raw(self, recs_addr, nbytes, roff_addr, n):
+    """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by score_result."""
+    self._chk(self._L.mh_score_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+
+  def score_add_records(self, recs, roff):
+    """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
+    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
+    o = np.ascontiguousarray(roff, dtype=np.int64)
+    self._chk(self._L.mh_score_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+
+  def score_add_store(self):
+    """Score the context's own BAM record store (bam_add_fastq / bam_add_output) in HBM."""
+    self._chk(self._L.mh_score_add_store(self._h))
+
+  def score_result(self):
+    """(mq_mat u64[100, 2 max_d + 1], d_err_mat u64[2 max_v + 2, 2 max_d + 1], counts dict)."""
+    max_d, max_v = self._score_shape
+    mq = np.zeros((100, 2 * max_d + 1), np.uint64)
+    dv = np.zeros((2 * max_v + 2, 2 * max_d + 1), np.uint64)
+    cnt = np.zeros(4, np.int64)
+    self._chk(self._L.mh_score_result(self._h, _ptr(mq), _ptr(dv), _ptr(cnt)))
+    return mq, dv, dict(zip(('seen', 'scored', 'skipped_unplaced', 'skipped_sample'), (int(x) for x in cnt)))
+
+  def score_reset(self):
+    self._chk(self._L.mh_score_reset(self._h))
 
   def bam_partition(self, splitters, tie_base):
     """The store's records by destination rank (mh_bam_partition): returns (segment offsets [n_dest + 1], records

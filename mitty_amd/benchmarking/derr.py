@@ -1,0 +1,61 @@
+"""derr-plot (reference mitty/benchmarking/derr.py): score every aligned read of a BAM of simulated reads and count
+reads by (size of each variant carried, d_err).  One device pass (mitty_amd/benchmarking/score.py)."""
+import logging
+
+import numpy as np
+
+from mitty_amd.benchmarking.score import score_bam
+
+logger = logging.getLogger(__name__)
+
+
+def process_bam(bam_fname, max_v_len=200, max_d=200, strict=False, sample_name=None, processes=2, out_csv=None,
+                device=0):
+  """derr.process_bam (derr.py:19-46): d_err_mat u64[2 max_v_len + 2, 2 max_d + 1]; row max_v_len + v per variant
+  size v a read carries (deletions negative), the last row for reads without variants."""
+  if max_v_len < 51:
+    logger.warning('Setting max_v_len to 51')
+    max_v_len = 51
+  _, d_err_mat, _ = score_bam(bam_fname, max_d=max_d, max_v_len=max_v_len, strict=strict, sample_name=sample_name,
+                              processes=processes, device=device)
+  if out_csv is not None:
+    logger.debug('Saving d_err matrix to {}'.format(out_csv))
+    np.savetxt(out_csv, d_err_mat, delimiter=',', fmt='%d')
+  return d_err_mat
+
+
+def plot_derr(derr_mat, plot):
+  """A two-panel figure of the d_err matrix: per variant size (deletions negative, 0 = SNP) the fraction of the reads
+  carrying such a variant that were placed exactly and within 10 bases, with the variant-free reads'
+  exact fraction as a level line; and the matrix itself as a log-count image.  Returns False, and draws nothing, when
+  matplotlib is not installed."""
+  from mitty_amd.benchmarking.mq import _pyplot
+  plt = _pyplot()
+  if plt is None:
+    logger.warning('matplotlib is not installed: {} not drawn (the CSV holds the matrix)'.format(plot))
+    return False
+  v_max = (derr_mat.shape[0] - 2) // 2
+  half = (derr_mat.shape[1] - 1) // 2
+  by_size, ref_row = derr_mat[:2 * v_max + 1].astype(float), derr_mat[-1].astype(float)
+  sizes = np.arange(-v_max, v_max + 1)
+  near = np.abs(np.arange(-half, half + 1)) <= min(10, half)
+  reads = by_size.sum(axis=1)
+  seen = reads > 0
+  fig, (ax_frac, ax_img) = plt.subplots(2, 1, figsize=(9, 9), constrained_layout=True)
+  ax_frac.plot(sizes[seen], by_size[seen, half] / reads[seen], '.', color='tab:green', label='placed exactly')
+  ax_frac.plot(sizes[seen], by_size[seen][:, near].sum(axis=1) / reads[seen], '.', color='tab:olive',
+               label='within {} bases'.format(min(10, half)))
+  if ref_row.sum() > 0:
+    ax_frac.axhline(ref_row[half] / ref_row.sum(), color='0.4', linewidth=1, label='reads without variants, exactly')
+  ax_frac.set_xlabel('size of a variant the read carries (deletions < 0, SNP = 0, insertions > 0)')
+  ax_frac.set_ylabel('fraction of reads')
+  ax_frac.set_ylim(-0.02, 1.02)
+  ax_frac.legend(loc='lower center', fontsize='small', ncol=3)
+  img = ax_img.imshow(np.log10(by_size + 1.0), origin='lower', aspect='auto', cmap='magma',
+                      extent=(-half - 0.5, half + 0.5, -v_max - 0.5, v_max + 0.5))
+  ax_img.set_xlabel('d_err (bases from the true position)')
+  ax_img.set_ylabel('variant size')
+  fig.colorbar(img, ax=ax_img, label='log10(reads + 1)')
+  fig.savefig(plot)
+  plt.close(fig)
+  return True

@@ -1,11 +1,11 @@
 """`mitty` command line (reference mitty/cli.py), MI355X build.
 
-Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), filter-variants (host C++), qname,
-list-read-models.  Additive options on generate-reads: --device,
+Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), mq-plot and derr-plot (GPU scoring, host
+BAM reader; additive --device), filter-variants (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
 --rng {mitty,philox}, --corrupt-seed (fused Philox corruption); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
 RCCL); the output files are identical to the one-GPU run.  Out of scope for this build (not on the
-generate-reads path): filter-bam, gc-cov, bq, bam2illumina, describe-read-model, mq-plot, derr-plot.
+generate-reads path): filter-bam, gc-cov, bq, bam2illumina, describe-read-model.
 """
 import logging
 import os
@@ -152,6 +152,39 @@ def god_aligner(fasta, bam, sample_name, fastq1, fastq2, max_templates, threads,
   from mitty_amd.benchmarking import god_aligner as god
   god.process_multi_threaded(fasta, bam, fastq1, fastq2, threads, max_templates, sample_name, device=device,
                              gpu_bgzf=gpu_bgzf, hbm_capacity=int(hbm_gb * 1e9))
+
+
+@cli.command('mq-plot', short_help='Create MQ plot from BAM')
+@click.argument('bam', type=click.Path(exists=True))
+@click.argument('csv')
+@click.argument('plot')
+@click.option('--max-d', type=int, default=200, help='Range of d_err to consider')
+@click.option('--strict-scoring', is_flag=True, help="Don't consider breakpoints when scoring alignment")
+@click.option('--sample-name', help='If the FASTQ contains multiple samples, process reads from only this sample')
+@click.option('--threads', default=2)
+@click.option('--device', default=0, help='HIP device ordinal')
+def mq_plot(bam, csv, plot, max_d, strict_scoring, sample_name, threads, device):
+  """Given a BAM from simulated reads, construct an MQ plot (reference cli.py:224-236)"""
+  from mitty_amd.benchmarking import mq
+  mq_mat = mq.process_bam(bam, max_d, strict_scoring, sample_name, threads, csv, device=device)
+  mq.plot_mq(mq_mat, plot)   # (logs and skips the figure when matplotlib is not installed; the CSV is written)
+
+
+@cli.command('derr-plot', short_help='Create alignment error plot from BAM')
+@click.argument('bam', type=click.Path(exists=True))
+@click.argument('csv')
+@click.argument('plot')
+@click.option('--max-v', type=int, default=200, help='Range of variant sizes to consider (51 min)')
+@click.option('--max-d', type=int, default=200, help='Range of d_err to consider')
+@click.option('--strict-scoring', is_flag=True, help="Don't consider breakpoints when scoring alignment")
+@click.option('--sample-name', help='If the FASTQ contains multiple samples, process reads from only this sample')
+@click.option('--threads', default=2)
+@click.option('--device', default=0, help='HIP device ordinal')
+def derr_plot(bam, csv, plot, max_v, max_d, strict_scoring, sample_name, threads, device):
+  """Given a BAM from simulated reads, show pattern of alignment errors (reference cli.py:239-252)"""
+  from mitty_amd.benchmarking import derr
+  derr_mat = derr.process_bam(bam, max_v, max_d, strict_scoring, sample_name, threads, csv, device=device)
+  derr.plot_derr(derr_mat, plot)
 
 
 def main():

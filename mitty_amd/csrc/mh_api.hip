@@ -469,6 +469,7 @@ int32_t mh_destroy(mh_ctx *ctx) {
   (void)hipEventDestroy(ctx->ev_writer);
   (void)hipStreamDestroy(ctx->wstream);
   bam_release(ctx->bam);
+  score_release(ctx->score);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1685,6 +1686,34 @@ int32_t mh_bam_write(mh_ctx *ctx, const char *bam_path, const char *header_text,
   if (out_records) *out_records = n;
   if (out_bytes) *out_bytes = B.bytes;
   return MH_OK;
+}
+
+// ---- alignment scoring (mh_score.hip) ---------------------------------------------------------------------------
+int32_t mh_score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_d, int32_t max_v_len,
+                       int32_t strict, const char *sample_prefix) {
+  CTX_GUARD(ctx);
+  return score_begin(ctx, n_refs, names, max_d, max_v_len, strict, sample_prefix);
+}
+
+int32_t mh_score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  CTX_GUARD(ctx);
+  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  return score_add_records(ctx, recs, len, roff, n);
+}
+
+int32_t mh_score_add_store(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return score_add_store(ctx);
+}
+
+int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts) {
+  CTX_GUARD(ctx);
+  return score_result(ctx, mq_mat, derr_mat, counts);
+}
+
+int32_t mh_score_reset(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return score_reset(ctx);
 }
 
 }  // extern "C"

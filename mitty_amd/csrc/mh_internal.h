@@ -219,6 +219,23 @@ struct BamStore {
   std::string spill_dir;       // mh_bam_set_spill_dir: spill to files there (the page cache, not anonymous memory)
 };
 
+// Alignment scorer (mh_score.hip): both matrices and the counts of one scoring session, resident until read back.
+struct ScoreState {
+  bool begun = false;
+  int32_t max_d = 0, max_v = 0, strict = 0, n_refs = 0, plen = 0;
+  int64_t n_mq = 0, n_dv = 0, n_all = 0;   // u64 cells of mq_mat, d_err_mat, and both + the 4 counts
+  DevBuf acc, delta;           // [mq_mat | d_err_mat | counts]: the session's sums / the chunk being scored
+  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
+  DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
+  DevBuf in[2];                // the chunk on the device: record offsets, then the records
+  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked staging, one per chunk in flight
+  size_t pin_cap[2] = {0, 0};
+  hipEvent_t ev[2] = {nullptr, nullptr};  // after the kernels of the chunk staged in pin[k]
+  bool ev_set[2] = {false, false};
+  int cur = 0;
+  int64_t base_rec = 0;        // records given to earlier calls (names a failing record)
+};
+
 struct StageTime {
   const char *name;
   hipEvent_t a, b;
@@ -387,6 +404,8 @@ struct mh_ctx {
 
   // god-aligner BAM records
   mh::BamStore bam;
+  // mq-plot / derr-plot scoring session
+  mh::ScoreState score;
 };
 
 namespace mh {
@@ -520,6 +539,14 @@ int32_t bam_bai_plan(mh_ctx *ctx, BaiPlan &plan, std::vector<int64_t> &offs, boo
 void bam_release(BamStore &B);
 void bam_free_spill(BamStore &B);
 int32_t newline_index(mh_ctx *ctx, const uint8_t *b, int64_t len, DevBuf &nl, int64_t *count);
+// alignment scoring (mh_score.hip)
+int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_d, int32_t max_v_len, int32_t strict,
+                    const char *sample_prefix);
+int32_t score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t score_add_store(mh_ctx *ctx);
+int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
+int32_t score_reset(mh_ctx *ctx);
+void score_release(ScoreState &S);
 int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_t *d1, int64_t len1, int64_t t_base,
                       int64_t *used0, int64_t *used1, int64_t *templates);
 

@@ -1,0 +1,499 @@
+// mh_score.hip — alignment scoring for mq-plot / derr-plot (reference mitty/benchmarking/mq.py:50-68,
+// derr.py:53-76 over readgenerate.parse_qname :259-291 and score_alignment_error :294-319) on the device.
+//
+//   BAM records in HBM (a chunk uploaded from the host reader, or the context's own god-aligner store)
+//     -> k_score   thread per record: the record's head (fixed fields + read name) staged in LDS with 16-byte loads,
+//                  sample-prefix filter, parse_qname of the mate's group (flag 0x80), chrom against the header name of
+//                  tid, d_err, then both matrices from the one pass:
+//                    mq_mat[mapq, d_err + max_d]          u64[100][2 max_d + 1]
+//                    d_err_mat[max_v + v, d_err + max_d]  u64[2 max_v + 2][2 max_d + 1]   (last row: empty v_list)
+//     -> k_score_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
+//
+// Contention: nearly every read of a good aligner lands in (MAPQ 60, d_err 0) and (ref or SNP row, d_err 0).  Lanes of
+// a wave with equal cells are combined into one add (ballot + popcount); the d_err = 0 column of both matrices is
+// kept in per-workgroup LDS counters; a workgroup walks many 256-record tiles and flushes those counters once, with
+// 64-bit global atomics.  Integer adds: the result does not depend on the order and is exact.
+//
+// Every read of a record stays inside [roff[i], roff[i + 1]): lengths taken from the record are clamped to it.  A
+// record whose name does not parse (or any other failure) sets the error word with its index and adds nothing.
+#include <algorithm>
+#include <cstring>
+
+#include "mh_bamread.h"
+#include "mh_internal.h"
+
+namespace mh {
+namespace {
+
+constexpr int SC_ROW = 192;       // LDS bytes per record head (4 + 32 fixed bytes, then the name; up to 15 bytes of lead)
+constexpr int SC_NV_LDS = 1026;   // d_err_mat rows with an LDS counter for their d_err = 0 column (max_v_len <= 512)
+constexpr int SC_FIELDS = 13;     // rid, chrom, cpy + 2 x (strand, pos, rlen, cigar, v_list)
+
+enum { SE_STRUCT = 1, SE_TID = 2, SE_PARSE = 3, SE_MATE = 4, SE_MAPQ = 5 };
+
+struct ScoreArgs {
+  const uint8_t *recs;
+  const int64_t *roff;
+  int64_t n, avail;            // records; bytes readable at recs
+  const char *names;           // header names, concatenated
+  const int32_t *name_off;     // [n_refs + 1]
+  int32_t n_refs;
+  const uint8_t *prefix;
+  int32_t plen;
+  int32_t max_d, max_v, strict;
+  unsigned long long *mq, *dv, *cnt;   // the chunk's sums
+  unsigned long long *err;
+  int64_t base_rec;
+};
+
+__device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+__device__ __forceinline__ uint32_t rd32(const uint8_t *p) {
+  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+// int() of q[a, b): optional sign, then digits only; values saturate at 2^40.  False when it is not such a number.
+__device__ __forceinline__ bool sc_int(const uint8_t *q, int a, int b, int64_t &v) {
+  if (a >= b) return false;
+  bool neg = false;
+  if (q[a] == '-' || q[a] == '+') { neg = q[a] == '-'; a++; }
+  if (a >= b) return false;
+  int64_t x = 0;
+  for (; a < b; a++) {
+    const uint32_t d = (uint32_t)q[a] - '0';
+    if (d > 9) return false;
+    x = x * 10 + d;
+    if (x > ((int64_t)1 << 40)) x = (int64_t)1 << 40;
+  }
+  v = neg ? -x : x;
+  return true;
+}
+
+// [int(v) for v in v_list.split(',') if v is not '']: false when an item is not a number; *items = the list's length
+__device__ __forceinline__ bool sc_vlist_ok(const uint8_t *q, int a, int b, int *items) {
+  int n = 0, st = a;
+  for (int i = a; i <= b; i++) {
+    if (i == b || q[i] == ',') {
+      if (i > st) {
+        int64_t v;
+        if (!sc_int(q, st, i, v)) return false;
+        n++;
+      }
+      st = i + 1;
+    }
+  }
+  *items = n;
+  return true;
+}
+
+// One add per distinct cell among the wave's lanes (cell < 0: none).  The d_err = 0 column goes to the workgroup's LDS
+// counters (row < lds_rows), everything else to the chunk's matrix in memory.  Called by every lane of the wave.
+__device__ __forceinline__ void wave_add(int32_t cell, int lane, int32_t ncol, int32_t zero_col, uint32_t *lds,
+                                         int32_t lds_rows, unsigned long long *g) {
+  uint64_t pend = __ballot(cell >= 0);
+  while (pend) {
+    const int leader = __ffsll((unsigned long long)pend) - 1;
+    const int32_t lc = __shfl(cell, leader, 64);
+    const uint64_t m = __ballot(cell == lc);
+    if (lane == leader) {
+      const uint32_t c = (uint32_t)__popcll(m);
+      const int32_t row = lc / ncol, col = lc - row * ncol;
+      if (col == zero_col && row < lds_rows) atomicAdd(&lds[row], c);
+      else atomicAdd(&g[lc], (unsigned long long)c);
+    }
+    if (cell == lc) cell = -1;
+    pend &= ~m;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t rows[256 * SC_ROW];
+  __shared__ uint32_t l_mq[100], l_dv[SC_NV_LDS], l_cnt[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t ncol = 2 * a.max_d + 1, n_vrow = 2 * a.max_v + 2;
+  const int32_t lds_vrows = n_vrow < SC_NV_LDS ? n_vrow : SC_NV_LDS;
+  for (int i = threadIdx.x; i < 100; i += 256) l_mq[i] = 0;
+  for (int i = threadIdx.x; i < SC_NV_LDS; i += 256) l_dv[i] = 0;
+  if (threadIdx.x < 4) l_cnt[threadIdx.x] = 0;
+  const int64_t tiles = (a.n + 255) / 256;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    __syncthreads();   // the counters are zero / the previous tile's rows are no longer read
+    // ---- stage the wave's 64 record heads: one 16-byte load per lane per record, all in flight together
+    const int64_t tw = tile * 256 + 64 * wave;
+    {
+      const int64_t tl = tw + lane;
+      const int64_t s0 = tl < a.n ? a.roff[tl] : 0, e0 = tl < a.n ? a.roff[tl + 1] : 0;
+#pragma unroll 8
+      for (int j = 0; j < 64; j++) {
+        const int64_t s = __shfl(s0, j, 64), e = __shfl(e0, j, 64);
+        const int64_t c0 = s & ~(int64_t)15;
+        int64_t nch = (e - c0 + 15) >> 4;
+        if (nch > SC_ROW / 16) nch = SC_ROW / 16;
+        if (tw + j < a.n && e > s && s >= 0 && c0 + 16 * nch <= a.avail && lane < nch)
+          *(uint4 *)(rows + (64 * wave + j) * SC_ROW + 16 * lane) = *(const uint4 *)(a.recs + c0 + 16 * lane);
+      }
+    }
+    __syncthreads();
+    // ---- the thread's record
+    const int64_t t = tile * 256 + threadIdx.x;
+    int32_t mq_cell = -1, col = 0, kind = 0;
+    int vs = 0, ve = 0, v_items = -1;      // the scored group's v_list in the name; -1: nothing to add
+    const uint8_t *q = nullptr;            // the read name
+    int seen = 0, scored = 0, skip_tid = 0, skip_smp = 0;
+    if (t < a.n) {
+      const int64_t s = a.roff[t], e = a.roff[t + 1];
+      const int64_t size = e - s;
+      seen = 1;
+      if (size < 36 || s < 0 || e > a.avail) {
+        kind = SE_STRUCT;
+      } else {
+        const int64_t c0 = s & ~(int64_t)15;
+        int64_t nch = (e - c0 + 15) >> 4;
+        if (nch > SC_ROW / 16) nch = SC_ROW / 16;
+        const bool row_ok = c0 + 16 * nch <= a.avail;
+        const int64_t rb = 16 * nch - (s - c0);   // the record's bytes in its row
+        const uint8_t *lp = a.recs + s;
+        if (row_ok && rb >= 36) {
+          const uint8_t *rp = rows + threadIdx.x * SC_ROW + (s - c0);
+          if (36 + (int64_t)rp[12] <= rb) lp = rp;   // a name longer than its row is read from memory
+        }
+        const int32_t tid = (int32_t)rd32(lp + 4), pos = (int32_t)rd32(lp + 8);
+        const int32_t mapq = lp[13], flag = (int32_t)rd16(lp + 18);
+        int nmax = lp[12];
+        if (nmax > size - 36) nmax = (int)(size - 36);
+        q = lp + 36;
+        int nlen = 0;
+        while (nlen < nmax && q[nlen] != 0) nlen++;
+        bool pass = true;
+        if (tid < 0) {
+          skip_tid = 1;   // fetch(reference=SN) per @SQ never yields these
+          pass = false;
+        } else if (tid >= a.n_refs) {
+          kind = SE_TID;
+          pass = false;
+        } else if (a.plen > 0) {   // qname.startswith(sample_name)
+          bool eq = nlen >= a.plen;
+          for (int k = 0; eq && k < a.plen; k++) eq = q[k] == a.prefix[k];
+          if (!eq) { skip_smp = 1; pass = false; }
+        }
+        if (pass) {
+          // qname.split('|'): rid, chrom, cpy, then (strand, pos, rlen, cigar, v_list) per read
+          int fs[SC_FIELDS], fe[SC_FIELDS];
+          int nf = 0, st = 0;
+          for (int i = 0; i <= nlen; i++) {
+            if (i == nlen || q[i] == '|') {
+              if (nf < SC_FIELDS) { fs[nf] = st; fe[nf] = i; }
+              nf++;
+              st = i + 1;
+            }
+          }
+          const int ng = nf >= 3 ? (nf - 3) / 5 : 0;   // zip(d[3::5], ..., d[7::5]): whole groups only
+          const int want = (flag & 0x80) ? 1 : 0;
+          int64_t iv;
+          if (nf < 3) kind = SE_PARSE;
+          if (!kind) {   // sample, _ = rid.split(':', 1); int(cpy)
+            bool colon = false;
+            for (int k = fs[0]; k < fe[0]; k++) colon |= q[k] == ':';
+            if (!colon || !sc_int(q, fs[2], fe[2], iv)) kind = SE_PARSE;
+          }
+          int items[2] = {0, 0};
+          for (int g = 0; !kind && g < ng && g < 2; g++) {
+            const int f = 3 + 5 * g;
+            if (!sc_int(q, fs[f], fe[f], iv) || !sc_int(q, fs[f + 1], fe[f + 1], iv) ||
+                !sc_int(q, fs[f + 2], fe[f + 2], iv) || fe[f + 3] <= fs[f + 3] ||
+                !sc_vlist_ok(q, fs[f + 4], fe[f + 4], &items[g]))
+              kind = SE_PARSE;
+          }
+          if (!kind && want >= ng) kind = (want == 1 && ng >= 1) ? SE_MATE : SE_PARSE;
+          if (!kind) {
+            const int f = 3 + 5 * want;
+            int64_t rpos = 0;
+            (void)sc_int(q, fs[f + 1], fe[f + 1], rpos);
+            int cs = fs[f + 3], ce = fe[f + 3];
+            if (q[cs] == '>') {   // '>p:nI' -> 'nI' (parse_qname: split(':')[-1])
+              int k = ce;
+              while (k > cs && q[k - 1] != ':') k--;
+              cs = k;
+            }
+            // reference_name == ri.chrom, as strings
+            const int32_t no = a.name_off[tid], nl = a.name_off[tid + 1] - no;
+            bool same = nl == fe[1] - fs[1];
+            for (int k = 0; same && k < nl; k++) same = a.names[no + k] == (char)q[fs[1] + k];
+            const int64_t p1 = (int64_t)pos + 1, md = a.max_d;
+            int64_t D = md;
+            if (!a.strict && ce <= cs) {
+              kind = SE_PARSE;   // ri.cigar[0] of an empty cigar raises
+            } else if (a.strict || q[cs] == '>') {
+              if (same) D = p1 - rpos > md ? md : (p1 - rpos < -md ? -md : p1 - rpos);
+            } else if (same) {
+              // cigar_parser.findall: (\d+)(\D); '=', 'M', 'X' are breakpoints, 'D' only advances
+              int64_t cp = rpos, cnt = 0;
+              bool have = false;
+              for (int k = cs; k < ce; k++) {
+                const uint32_t d = (uint32_t)q[k] - '0';
+                if (d <= 9) {
+                  cnt = cnt * 10 + d;
+                  if (cnt > ((int64_t)1 << 40)) cnt = (int64_t)1 << 40;
+                  have = true;
+                  continue;
+                }
+                if (have) {
+                  const uint8_t op = q[k];
+                  if (op == '=' || op == 'M' || op == 'X') {
+                    const int64_t df = p1 - cp;
+                    if ((df < 0 ? -df : df) < (D < 0 ? -D : D)) D = df;
+                    cp += cnt;
+                  } else if (op == 'D') {
+                    cp += cnt;
+                  }
+                }
+                cnt = 0;
+                have = false;
+              }
+            }
+            if (!kind && mapq >= 100) kind = SE_MAPQ;   // mq_mat[r.mapq, ...] raises IndexError
+            if (!kind) {
+              col = (int32_t)(D + md);
+              mq_cell = mapq * ncol + col;
+              vs = fs[f + 4];
+              ve = fe[f + 4];
+              v_items = items[want];
+              scored = 1;
+            }
+          }
+        }
+      }
+      if (kind) atomicMin(a.err, ((unsigned long long)(a.base_rec + t) << 4) | (unsigned long long)kind);
+    }
+    {   // the four counts: one LDS add per wave each
+      const uint64_t b[4] = {__ballot(seen), __ballot(scored), __ballot(skip_tid), __ballot(skip_smp)};
+      if (lane < 4 && b[lane]) atomicAdd(&l_cnt[lane], (uint32_t)__popcll(b[lane]));
+    }
+    // ---- both matrices
+    wave_add(mq_cell, lane, ncol, a.max_d, l_mq, 100, a.mq);
+    // d_err_mat: a row per v of the v_list inside +-max_v, the last row for an empty list; the wave goes round once per
+    // list position
+    int32_t left = v_items < 0 ? 0 : (v_items == 0 ? 1 : v_items);
+    int vi = vs;
+    while (__ballot(left > 0)) {
+      int32_t cell = -1;
+      if (left > 0) {
+        left--;
+        if (v_items == 0) {
+          cell = (n_vrow - 1) * ncol + col;
+        } else {
+          int st = vi;
+          while (st < ve && q[st] == ',') st++;   // empty items are skipped
+          int en = st;
+          while (en < ve && q[en] != ',') en++;
+          int64_t v = 0;
+          (void)sc_int(q, st, en, v);
+          vi = en + 1;
+          const int64_t r = (int64_t)a.max_v + v;
+          if (r >= 0 && r < 2 * (int64_t)a.max_v + 1) cell = (int32_t)r * ncol + col;
+        }
+      }
+      wave_add(cell, lane, ncol, a.max_d, l_dv, lds_vrows, a.dv);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 100; i += 256)
+    if (l_mq[i]) atomicAdd(&a.mq[(int64_t)i * ncol + a.max_d], (unsigned long long)l_mq[i]);
+  for (int i = threadIdx.x; i < lds_vrows; i += 256)
+    if (l_dv[i]) atomicAdd(&a.dv[(int64_t)i * ncol + a.max_d], (unsigned long long)l_dv[i]);
+  if (threadIdx.x < 4 && l_cnt[threadIdx.x]) atomicAdd(&a.cnt[threadIdx.x], (unsigned long long)l_cnt[threadIdx.x]);
+}
+
+__global__ void k_score_commit(const unsigned long long *delta, unsigned long long *acc, int64_t n,
+                               const unsigned long long *err) {
+  if (*err != ~0ull) return;   // a record failed: nothing of this chunk, or of any later one, is kept
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    if (delta[i]) acc[i] += delta[i];
+}
+
+// the chunk's sums zeroed, the records scored, the sums committed; all queued on the context's stream
+int32_t score_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail, const char *names,
+                     const int32_t *name_off, int32_t n_refs) {
+  ScoreState &S = ctx->score;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipMemsetAsync(S.delta.p, 0, sizeof(uint64_t) * S.n_all, st));
+  unsigned long long *d = (unsigned long long *)S.delta.p;
+  ScoreArgs a{recs, roff, n, avail, names, name_off, n_refs, (const uint8_t *)S.prefix.p, S.plen, S.max_d, S.max_v,
+              S.strict, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.err.p, S.base_rec};
+  // a workgroup's LDS counters are 32-bit: at most 4096 tiles (2^20 records, < 2^8 list items each) per workgroup
+  const int64_t tiles = (n + 255) / 256;
+  const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
+  hipLaunchKernelGGL(k_score, dim3((unsigned)grid), dim3(256), 0, st, a);
+  HIPCHK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_score_commit, dim3(grid_for(S.n_all, 256, 1024)), dim3(256), 0, st,
+                     (const unsigned long long *)S.delta.p, (unsigned long long *)S.acc.p, S.n_all,
+                     (const unsigned long long *)S.err.p);
+  HIPCHK(ctx, hipGetLastError());
+  S.base_rec += n;
+  return MH_OK;
+}
+
+int32_t score_clear(mh_ctx *ctx) {
+  ScoreState &S = ctx->score;
+  for (int k = 0; k < 2; k++)
+    if (S.ev_set[k]) {
+      HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
+      S.ev_set[k] = false;
+    }
+  HIPCHK(ctx, hipMemsetAsync(S.acc.p, 0, sizeof(uint64_t) * S.n_all, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, ctx->stream));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  S.base_rec = 0;
+  return MH_OK;
+}
+
+}  // namespace
+
+int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_d, int32_t max_v_len, int32_t strict,
+                    const char *sample_prefix) {
+  ScoreState &S = ctx->score;
+  if (n_refs < 0 || (n_refs > 0 && !names)) return arg_fail(ctx, MH_E_ARG, "bad reference list");
+  if (max_d < 0 || max_d > (1 << 20)) return arg_fail(ctx, MH_E_ARG, "max_d must be 0..2^20");
+  if (max_v_len < 51) max_v_len = 51;   // derr.py:21-23
+  if (max_v_len > (1 << 20)) return arg_fail(ctx, MH_E_ARG, "max_v_len must be at most 2^20");
+  const int64_t ncol = 2 * (int64_t)max_d + 1;
+  if ((2 * (int64_t)max_v_len + 2) * ncol >= INT32_MAX) return arg_fail(ctx, MH_E_ARG, "d_err matrix of 2^31 cells or more");
+  S.begun = false;
+  S.max_d = max_d;
+  S.max_v = max_v_len;
+  S.strict = strict ? 1 : 0;
+  S.n_mq = 100 * ncol;
+  S.n_dv = (2 * (int64_t)max_v_len + 2) * ncol;
+  S.n_all = S.n_mq + S.n_dv + 4;
+  std::vector<int32_t> off(1, 0);
+  std::string cat;
+  const char *p = names;
+  for (int32_t i = 0; i < n_refs; i++) {
+    const size_t l = strlen(p);
+    cat.append(p, l);
+    p += l + 1;
+    off.push_back((int32_t)cat.size());
+  }
+  const std::string pre = sample_prefix ? sample_prefix : "";
+  S.n_refs = n_refs;
+  S.plen = (int32_t)pre.size();
+  hipStream_t st = ctx->stream;
+  for (int k = 0; k < 2; k++)
+    if (S.ev_set[k]) {
+      HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
+      S.ev_set[k] = false;
+    }
+  MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
+  MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
+  MH_TRY(ensure(ctx, S.err, 64));
+  MH_TRY(ensure(ctx, S.names, cat.size() + 16));
+  MH_TRY(ensure(ctx, S.name_off, sizeof(int32_t) * off.size()));
+  MH_TRY(ensure(ctx, S.prefix, pre.size() + 16));
+  if (!cat.empty()) HIPCHK(ctx, hipMemcpyAsync(S.names.p, cat.data(), cat.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(S.name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
+  if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(S.prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
+  for (int k = 0; k < 2; k++)
+    if (!S.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&S.ev[k], hipEventDisableTiming));
+  MH_TRY(score_clear(ctx));   // (synchronises: the host strings above are done with)
+  S.begun = true;
+  return MH_OK;
+}
+
+int32_t score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  ScoreState &S = ctx->score;
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
+  if (n == 0) return MH_OK;
+  // the same structural check the reader applies: nothing malformed reaches the device
+  if (roff[0] < 0 || roff[n] > len) return arg_fail(ctx, MH_E_ARG, "record offsets outside the buffer");
+  for (int64_t i = 0; i < n; i++) {
+    std::string why;
+    if (roff[i + 1] < roff[i] || roff[i + 1] > len || !bam_record_ok(recs + roff[i], roff[i + 1] - roff[i], &why))
+      return arg_fail(ctx, MH_E_ARG, "malformed BAM record " + std::to_string(S.base_rec + i) + ": " +
+                                         (why.empty() ? "record offsets decrease" : why));
+  }
+  const int k = S.cur;
+  if (S.ev_set[k]) {   // the chunk staged here two calls ago has been scored
+    HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
+    S.ev_set[k] = false;
+  }
+  const int64_t bytes = roff[n] - roff[0];
+  const size_t o_recs = ((size_t)(n + 1) * 8 + 15) & ~(size_t)15, need = o_recs + (size_t)bytes + 64;
+  if (S.pin_cap[k] < need) {
+    if (S.pin[k]) (void)hipHostFree(S.pin[k]);
+    S.pin[k] = nullptr;
+    S.pin_cap[k] = 0;
+    const size_t cap = need + need / 4;
+    HIPCHK(ctx, hipHostMalloc((void **)&S.pin[k], cap, hipHostMallocDefault));
+    S.pin_cap[k] = cap;
+  }
+  int64_t *po = (int64_t *)S.pin[k];
+  for (int64_t i = 0; i <= n; i++) po[i] = roff[i] - roff[0];
+  memcpy(S.pin[k] + o_recs, recs + roff[0], (size_t)bytes);
+  memset(S.pin[k] + o_recs + bytes, 0, 64);
+  MH_TRY(ensure(ctx, S.in[k], need));
+  HIPCHK(ctx, hipMemcpyAsync(S.in[k].p, S.pin[k], need, hipMemcpyHostToDevice, ctx->stream));
+  MH_TRY(score_launch(ctx, (const uint8_t *)S.in[k].p + o_recs, (const int64_t *)S.in[k].p, n, bytes + 64,
+                      (const char *)S.names.p, (const int32_t *)S.name_off.p, S.n_refs));
+  HIPCHK(ctx, hipEventRecord(S.ev[k], ctx->stream));
+  S.ev_set[k] = true;
+  S.cur ^= 1;
+  return MH_OK;
+}
+
+int32_t score_add_store(mh_ctx *ctx) {
+  ScoreState &S = ctx->score;
+  BamStore &B = ctx->bam;
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
+  if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
+  if (B.n_rec == 0) return MH_OK;
+  if (B.spilled > 0)
+    return arg_fail(ctx, MH_E_STATE, "the record store has spilled to the host (mh_bam_set_capacity): score its BAM file");
+  // a direct sorted write keeps the records in coordinate order only; the sums do not depend on the order
+  const uint8_t *recs = (const uint8_t *)(B.direct ? B.srecs.p : B.recs.p);
+  const int64_t *roff = (const int64_t *)(B.direct ? B.soff.p : B.roff.p);
+  MH_TRY(score_launch(ctx, recs, roff, B.n_rec, B.bytes, (const char *)B.names.p, (const int32_t *)B.name_off.p,
+                      (int32_t)B.ref_names.size()));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return MH_OK;
+}
+
+int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts) {
+  ScoreState &S = ctx->score;
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
+  uint64_t herr = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&herr, S.err.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (herr != ~(uint64_t)0) {
+    static const char *what[] = {"", "record shorter than its fixed fields", "tid outside the header's references",
+                                 "qname does not parse (readgenerate.parse_qname)",
+                                 "read2 record whose qname has one read group",
+                                 "MAPQ of 100 or more (mq_mat has 100 rows)"};
+    const int kind = (int)(herr & 15);
+    return arg_fail(ctx, MH_E_ARG, "scoring: record " + std::to_string(herr >> 4) + ": " +
+                                       (kind >= 1 && kind <= 5 ? what[kind] : "unknown failure"));
+  }
+  const uint64_t *acc = (const uint64_t *)S.acc.p;
+  if (mq_mat) HIPCHK(ctx, hipMemcpyAsync(mq_mat, acc, 8 * S.n_mq, hipMemcpyDeviceToHost, ctx->stream));
+  if (derr_mat) HIPCHK(ctx, hipMemcpyAsync(derr_mat, acc + S.n_mq, 8 * S.n_dv, hipMemcpyDeviceToHost, ctx->stream));
+  if (counts) HIPCHK(ctx, hipMemcpyAsync(counts, acc + S.n_mq + S.n_dv, 32, hipMemcpyDeviceToHost, ctx->stream));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return MH_OK;
+}
+
+int32_t score_reset(mh_ctx *ctx) {
+  if (!ctx->score.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
+  return score_clear(ctx);
+}
+
+void score_release(ScoreState &S) {
+  release(S.acc); release(S.delta); release(S.err); release(S.names); release(S.name_off); release(S.prefix);
+  for (int k = 0; k < 2; k++) {
+    release(S.in[k]);
+    if (S.pin[k]) (void)hipHostFree(S.pin[k]);
+    if (S.ev[k]) (void)hipEventDestroy(S.ev[k]);
+    S.pin[k] = nullptr;
+    S.ev[k] = nullptr;
+  }
+  S.begun = false;
+}
+
+}  // namespace mh

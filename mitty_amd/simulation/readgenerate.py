@@ -247,3 +247,43 @@ def parse_qname(qname):
 
 
 cigar_parser = re.compile(r'(\d+)(\D)')
+
+
+_ALIGNED_OPS = ('=', 'M', 'X')
+
+
+def breakpoints(ri):
+  """The 1-based reference positions where a piece of the read that lies along the reference ('=', 'M' or 'X' op of
+  the qname CIGAR) starts: POS, and the far side of every deletion or mismatch run inside the read."""
+  at, starts = ri.pos, []
+  for m in cigar_parser.finditer(ri.cigar):
+    n, op = int(m.group(1)), m.group(2)
+    if op in _ALIGNED_OPS:
+      starts.append(at)
+      at += n
+    elif op == 'D':
+      at += n
+  return starts
+
+
+def score_alignment_error(r, ri, max_d=200, strict=False):
+  """d_err of aligned read `r` (anything with `pos`, 0-based, and `reference_name`) against its ReadInfo; the counterpart
+  of the reference's readgenerate.score_alignment_error (readgenerate.py:294-319) and the per-record statement of the
+  rule the device scorer (mh_score.hip) applies to whole BAMs.
+
+  On another chrom than the qname's: max_d.  strict: the offset of the placement from POS, clamped to +-max_d.
+  Otherwise the read counts as correct at any of its breakpoints(): the offset from the closest one (the first of two
+  equally close) when it is strictly inside max_d, else max_d.  parse_qname has already stripped '>p:' from the CIGAR
+  of a read from inside an insertion, so the reference never sees its '>' and scores such a read ('nI' only: no
+  breakpoint) max_d wherever it is placed unless strict; that is kept.  A CIGAR that still starts with '>' after the
+  strip is scored by the strict rule, and an empty one is an error unless strict, as in the reference."""
+  strict = strict or ri.cigar.startswith('>')
+  if not strict and not ri.cigar:
+    raise ValueError('empty CIGAR in qname')
+  if r.reference_name != ri.chrom:
+    return max_d
+  placed = r.pos + 1
+  if strict:
+    return min(max_d, max(-max_d, placed - ri.pos))
+  inside = [placed - b for b in breakpoints(ri) if abs(placed - b) < max_d]
+  return min(inside, key=abs) if inside else max_d
