@@ -68,6 +68,15 @@ int32_t mh_sync(mh_ctx *ctx);
  * never publishes; returns MH_E_STATE when the timed-out wait was reported (the expected result), then checks that a
  * correct scan after it succeeds. */
 int32_t mh_selftest_scan_fault(mh_ctx *ctx);
+/* Known-answer hook of the device scans (mh_scan.h; no reference counterpart: every prefix sum of the path goes through
+ * them): in[0, n * fields) (host; element i's `fields` int64 values adjacent, fields 1..3, summed field-wise) scanned
+ * on the device through the context's own scan scratch.  kind 0: the three-kernel scan with sums; 1: the same with max
+ * (fields 1); 2: the single-pass look-back scan (inputs >= 0 and every field's total < 2^46, else MH_E_ARG); 3: the
+ * reduction only.  incl / excl (host, n * fields each; unused by kind 3) get the inclusive and exclusive prefixes,
+ * total (fields values) the grand total.  repeat (kinds 0 and 2; else 1): the scan queued that many times, the last
+ * launch's results returned.  info[0], info[1]: the last look-back launch's epoch and ticket base (kind 2; else 0). */
+int32_t mh_selftest_scan(mh_ctx *ctx, int32_t kind, int32_t fields, const int64_t *in, int64_t n, int32_t repeat,
+                         int64_t *incl, int64_t *excl, int64_t *total, int64_t *info);
 /* Self-test of the permutation's radix sort (mh_sort.h; the stable (target, step) sort that replaces replaying
  * illumina.py:70's shuffle): keys[0, n) (host) sorted on the device over bits [0, end_bit); keys_out / vals_out (host,
  * n each) get the sorted keys and their input indices, equal keys in input order. */

@@ -17,7 +17,7 @@ MH_RNG_MITTY, MH_RNG_PHILOX = 0, 1
 
 # Every exported symbol of include/mitty_hip.h (tests check the library exports all of them).
 EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_error', 'mh_sync',
-           'mh_selftest_scan_fault', 'mh_selftest_sort',
+           'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort',
            'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes',
            'mh_release_haplotype', 'mh_expand_variant', 'mh_sample_templates', 'mh_sample_templates_span', 'mh_set_templates',
            'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
@@ -74,6 +74,7 @@ def lib():
   _sig(L, 'mh_last_error', [c_vp], ctypes.c_char_p)
   _sig(L, 'mh_sync', [c_vp])
   _sig(L, 'mh_selftest_scan_fault', [c_vp])
+  _sig(L, 'mh_selftest_scan', [c_vp, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_selftest_sort', [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp])
   _sig(L, 'mh_read_model_params', [c_i64, c_dbl, ctypes.POINTER(c_dbl), P_i64])
   _sig(L, 'mh_work_units', [c_u64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, P_i64])
@@ -1127,6 +1128,23 @@ class Context:
     ko, vo = np.empty_like(k), np.empty_like(k)
     self._chk(self._L.mh_selftest_sort(self._h, k.ctypes.data, k.size, int(end_bit), ko.ctypes.data, vo.ctypes.data))
     return ko, vo
+
+  def selftest_scan(self, kind, x, repeat=1):
+    """mh_selftest_scan: (inclusive, exclusive, total, (epoch, ticket base)) of the int64 array x — shape (n,) or
+    (n, fields), fields 1..3 — by the device scans.  kind 0: device_scan with sums, 1: with max, 2: the look-back
+    scan, 3: the reduction only (inclusive and exclusive are then None)."""
+    x = np.ascontiguousarray(x, dtype=np.int64)
+    if x.ndim not in (1, 2):
+      raise ValueError('selftest_scan: a 1-d or 2-d array')
+    fields = 1 if x.ndim == 1 else x.shape[1]
+    n = x.shape[0]
+    scans = int(kind) != 3
+    incl = np.empty_like(x) if scans else None
+    excl = np.empty_like(x) if scans else None
+    total, info = np.zeros(max(fields, 1), np.int64), np.zeros(2, np.int64)
+    self._chk(self._L.mh_selftest_scan(self._h, int(kind), int(fields), _ptr(x), n, int(repeat), _ptr(incl),
+                                       _ptr(excl), _ptr(total), _ptr(info)))
+    return incl, excl, (total[0] if x.ndim == 1 else total), (int(info[0]), int(info[1]))
 
   def selftest_scan_fault(self):
     """(return code, message) of mh_selftest_scan_fault: MH_E_STATE when a timed-out look-back scan is reported."""

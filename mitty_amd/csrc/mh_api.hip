@@ -15,6 +15,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 
 #include "mh_bgzf.h"
 #include <vector>
@@ -353,6 +354,80 @@ CorruptCfg corrupt_cfg(const mh_ctx *ctx, uint64_t unit_key, int64_t t_base) {
 }
 }  // namespace mh
 
+namespace {
+// mh_selftest_scan's elements: int64_t, and structs of 2 and 3 int64 fields summed field-wise (as NS of the splice,
+// Off3 of the corruption pass and E3 of the FASTQ writer); element i's fields are adjacent in the host arrays
+struct Sc2 {
+  int64_t a, b;
+  __device__ Sc2 operator+(const Sc2 &o) const { return Sc2{a + o.a, b + o.b}; }
+};
+struct Sc3 {
+  int64_t a, b, c;
+  __device__ Sc3 operator+(const Sc3 &o) const { return Sc3{a + o.a, b + o.b, c + o.c}; }
+};
+template <typename T>
+struct LoadArr {
+  const T *in;
+  __device__ T operator()(int64_t i) const { return in[i]; }
+};
+template <typename T>
+struct StoreBoth {   // both prefixes to element i of two arrays: a wrong value never becomes a wrong address
+  T *incl, *excl;
+  __device__ void operator()(int64_t i, const T &in, const T &ex) const {
+    incl[i] = in;
+    excl[i] = ex;
+  }
+};
+
+// One known-answer scan of n elements of T through ctx->scan_partials, sized as the production call sites size it.
+template <typename T>
+int32_t selftest_scan_run(mh_ctx *ctx, int32_t kind, const int64_t *in, int64_t n, int32_t repeat, int64_t *incl,
+                          int64_t *excl, int64_t *total, int64_t *info) {
+  hipStream_t st = ctx->stream;
+  MH_TRY(ensure(ctx, ctx->scan_partials,
+                kind == 2 ? scan_lb_scratch_bytes<T>(n) : sizeof(T) * (size_t)scan_partials_count(n) + 64));
+  DevBuf b;
+  const size_t ab = (sizeof(T) * (size_t)n + 255) & ~(size_t)255;
+  MH_TRY(ensure(ctx, b, 3 * ab + 256));
+  T *d_in = (T *)b.p, *d_incl = (T *)((char *)b.p + ab), *d_excl = (T *)((char *)b.p + 2 * ab);
+  T *d_tot = (T *)((char *)b.p + 3 * ab);
+  const int32_t rc = [&]() -> int32_t {
+    if (n) HIPCHK(ctx, hipMemcpyAsync(d_in, in, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(d_incl, 0xff, 2 * ab + 256, st));   // (an element the scan skipped shows)
+    const LoadArr<T> load{d_in};
+    const StoreBoth<T> store{d_incl, d_excl};
+    for (int32_t r = 0; r < repeat; r++) {
+      if (kind == 0)
+        HIPCHK(ctx, device_scan<T>(st, n, load, store, OpSum{}, T{}, (T *)ctx->scan_partials.p, d_tot));
+      else if (kind == 1) {
+        if constexpr (std::is_same<T, int64_t>::value)
+          HIPCHK(ctx, device_scan<T>(st, n, load, store, OpMax{}, INT64_MIN, (T *)ctx->scan_partials.p, d_tot));
+      } else if (kind == 2)
+        HIPCHK(ctx, device_scan_sum<T>(st, n, load, store, ctx->scan_partials.p, d_tot));
+      else
+        HIPCHK(ctx, device_reduce<T>(st, n, load, OpSum{}, T{}, (T *)ctx->scan_partials.p, d_tot));
+    }
+    if (kind == 2) {
+      std::lock_guard<std::mutex> lk(lb_mu());
+      auto it = lb_states().find(ctx->scan_partials.p);
+      if (it == lb_states().end()) return arg_fail(ctx, MH_E_HIP, "the look-back scratch has no state after a launch");
+      info[0] = (int64_t)it->second.epoch;
+      info[1] = (int64_t)(it->second.ticket - (uint32_t)scan_partials_count(n));   // (LB_TILE == SCAN_TILE)
+    }
+    if (n && kind != 3) {
+      HIPCHK(ctx, hipMemcpyAsync(incl, d_incl, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, st));
+      HIPCHK(ctx, hipMemcpyAsync(excl, d_excl, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(total, d_tot, sizeof(T), hipMemcpyDeviceToHost, st));
+    SYNCCHK(ctx, hipStreamSynchronize(st));
+    return MH_OK;
+  }();
+  release(b);   // (after a device synchronisation: cache_put)
+  return rc;
+}
+static_assert(LB_TILE == SCAN_TILE, "selftest_scan_run counts look-back tiles with scan_partials_count");
+}  // namespace
+
 extern "C" {
 
 int32_t mh_version(void) { return 1; }
@@ -505,9 +580,6 @@ struct StoreCheck {   // element i's exclusive prefix must be i
 };
 }  // namespace
 
-// A look-back scan whose tile 0 never runs (device_scan_sum's skip_tile0): every waiting tile times out, the fault
-// word is set, and the synchronisation after it fails with MH_E_STATE — the expected result.  A correct scan after it
-// then succeeds (the word was cleared).
 int32_t mh_selftest_sort(mh_ctx *ctx, const uint32_t *keys, int64_t n, int32_t end_bit, uint32_t *keys_out,
                          uint32_t *vals_out) {
   CTX_GUARD(ctx);
@@ -534,6 +606,38 @@ int32_t mh_selftest_sort(mh_ctx *ctx, const uint32_t *keys, int64_t n, int32_t e
   return rc;
 }
 
+// Known-answer hook of the scans (mh_scan.h): `in` (host, n elements of `fields` int64 each) scanned on the device,
+// both prefixes and the grand total back to the host.  kind 0: device_scan with OpSum; 1: device_scan with OpMax
+// (identity INT64_MIN, one field); 2: device_scan_sum (its value contract is checked here: inputs >= 0, every field's
+// total < 2^46); 3: device_reduce with OpSum (total only).  The partials / look-back scratch is ctx->scan_partials,
+// so successive calls share it as the production call sites do.  repeat (kinds 0 and 2): the scan queued that many
+// times back to back, the last launch's results returned.  info: the last look-back launch's epoch and ticket base
+// (kind 2; else 0, 0).
+int32_t mh_selftest_scan(mh_ctx *ctx, int32_t kind, int32_t fields, const int64_t *in, int64_t n, int32_t repeat,
+                         int64_t *incl, int64_t *excl, int64_t *total, int64_t *info) {
+  CTX_GUARD(ctx);
+  if (kind < 0 || kind > 3 || fields < 1 || fields > 3 || (kind == 1 && fields != 1) || n < 0 ||
+      n > ((int64_t)1 << 27) || repeat < 1 || repeat > (1 << 20) || ((kind == 1 || kind == 3) && repeat != 1) ||
+      !total || !info || (n > 0 && (!in || (kind != 3 && (!incl || !excl)))))
+    return arg_fail(ctx, MH_E_ARG, "bad scan self-test arguments");
+  if (kind == 2) {
+    uint64_t sum[3] = {0, 0, 0};
+    for (int64_t i = 0; i < n * fields; i++) {
+      if (in[i] < 0) return arg_fail(ctx, MH_E_ARG, "look-back scan: a negative input");
+      uint64_t &s = sum[i % fields];
+      s += (uint64_t)in[i];   // (s < 2^46 before, in[i] < 2^63: no wrap)
+      if (s >= ((uint64_t)1 << 46)) return arg_fail(ctx, MH_E_ARG, "look-back scan: a field's total is 2^46 or more");
+    }
+  }
+  info[0] = info[1] = 0;
+  if (fields == 1) return selftest_scan_run<int64_t>(ctx, kind, in, n, repeat, incl, excl, total, info);
+  if (fields == 2) return selftest_scan_run<Sc2>(ctx, kind, in, n, repeat, incl, excl, total, info);
+  return selftest_scan_run<Sc3>(ctx, kind, in, n, repeat, incl, excl, total, info);
+}
+
+// A look-back scan whose tile 0 never runs (device_scan_sum's skip_tile0): every waiting tile times out, the fault
+// word is set, and the synchronisation after it fails with MH_E_STATE — the expected result.  A correct scan after it
+// then succeeds (the word was cleared).
 int32_t mh_selftest_scan_fault(mh_ctx *ctx) {
   CTX_GUARD(ctx);
   hipStream_t st = ctx->stream;
