@@ -132,6 +132,14 @@ int32_t mh_release_variants(mh_ctx *ctx, int32_t vset);
  * non-'D' nodes).  Any pointer may be NULL. */
 int32_t mh_get_nodes(mh_ctx *ctx, int32_t slot, int64_t *ps, int64_t *pr, uint8_t *op, int64_t *oplen,
                      char *hap, int64_t hap_cap, int64_t *hap_len);
+/* Copy back what the splice derives from a slot's haplotype (a test entry point; nothing on the hot path calls it):
+ * rc, the reverse complement (*hap_len bytes, rc_cap >= *hap_len); run_start / run_end, the sorted [start, end)
+ * offsets of the maximal runs of 'N' (*n_runs entries each, run_cap >= *n_runs); bkt, the node-search bucket table
+ * (*n_bkt + 1 entries: bkt[k] = first node whose key is >= p_min + 256 k; bkt_cap >= *n_bkt + 1).  Any pointer may
+ * be NULL; a capacity too small for a non-NULL buffer is MH_E_CAPACITY (the counts are still returned). */
+int32_t mh_get_haplotype_aux(mh_ctx *ctx, int32_t slot, char *rc, int64_t rc_cap, int64_t *hap_len,
+                             int64_t *run_start, int64_t *run_end, int64_t run_cap, int64_t *n_runs,
+                             int32_t *bkt, int64_t bkt_cap, int64_t *n_bkt);
 int32_t mh_release_haplotype(mh_ctx *ctx, int32_t slot);
 /* The nodes ONE variant adds at cursors (samp_pos, ref_pos) of a region starting at ref_start_pos — the node rules
  * of the device splice (the same function runs inside it), exposed for the reference's per-variant helpers

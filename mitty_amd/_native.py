@@ -18,7 +18,7 @@ MH_RNG_MITTY, MH_RNG_PHILOX = 0, 1
 # Every exported symbol of include/mitty_hip.h (tests check the library exports all of them).
 EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_error', 'mh_sync',
            'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort',
-           'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes',
+           'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes', 'mh_get_haplotype_aux',
            'mh_release_haplotype', 'mh_expand_variant', 'mh_sample_templates', 'mh_sample_templates_span', 'mh_set_templates',
            'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
            'mh_read_batch', 'mh_set_corruption', 'mh_set_corruption_stream', 'mh_get_corruption_stream', 'mh_stage_times', 'mh_enable_timing', 'mh_sample_units', 'mh_sample_units_async', 'mh_templates_count',
@@ -85,6 +85,7 @@ def lib():
   _sig(L, 'mh_build_haplotype', [c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                  P_i64, P_i64, P_i64])
   _sig(L, 'mh_get_nodes', [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, P_i64])
+  _sig(L, 'mh_get_haplotype_aux', [c_vp, c_i32, c_vp, c_i64, P_i64, c_vp, c_vp, c_i64, P_i64, c_vp, c_i64, P_i64])
   _sig(L, 'mh_release_haplotype', [c_vp, c_i32])
   _sig(L, 'mh_bgzf_compress_device', [c_vp, c_vp, c_i64, c_vp, c_i64, P_i64])
   _sig(L, 'mh_bgzf_compress_gpu', [c_vp, c_vp, c_i64, c_vp, c_i64, P_i64])
@@ -577,6 +578,19 @@ class Context:
     self._chk(self._L.mh_get_nodes(self._h, slot, _ptr(ps), _ptr(pr), _ptr(op), _ptr(ol), _ptr(hap),
                                    hl.value if with_hap else 0, ctypes.byref(hl)))
     return ps[:n_nodes], pr[:n_nodes], op[:n_nodes], ol[:n_nodes], (hap[:hl.value].tobytes() if with_hap else None)
+
+  def get_haplotype_aux(self, slot):
+    """What the splice derives from a slot's haplotype (tests): (rc bytes, N-run starts i64, N-run ends i64, bucket
+    table i32 of n_bkt + 1 entries)."""
+    hl, nr, nb = c_i64(), c_i64(), c_i64()
+    self._chk(self._L.mh_get_haplotype_aux(self._h, slot, None, 0, ctypes.byref(hl), None, None, 0, ctypes.byref(nr),
+                                           None, 0, ctypes.byref(nb)))
+    rc = np.empty(max(hl.value, 1), np.uint8)
+    rs, re_ = np.empty(max(nr.value, 1), np.int64), np.empty(max(nr.value, 1), np.int64)
+    bkt = np.empty(nb.value + 1, np.int32)
+    self._chk(self._L.mh_get_haplotype_aux(self._h, slot, _ptr(rc), hl.value, ctypes.byref(hl), _ptr(rs), _ptr(re_),
+                                           nr.value, ctypes.byref(nr), _ptr(bkt), nb.value + 1, ctypes.byref(nb)))
+    return rc[:hl.value].tobytes(), rs[:nr.value], re_[:nr.value], bkt
 
   def release_haplotype(self, slot):
     self._chk(self._L.mh_release_haplotype(self._h, slot))

@@ -1003,6 +1003,31 @@ int32_t mh_get_nodes(mh_ctx *ctx, int32_t slot, int64_t *ps, int64_t *pr, uint8_
   return MH_OK;
 }
 
+// The structures the splice derives from the haplotype bytes and the node keys, for tests (nothing on the hot path
+// reads them back): reverse complement, sorted N-run lists, node-search bucket table.
+int32_t mh_get_haplotype_aux(mh_ctx *ctx, int32_t slot, char *rc, int64_t rc_cap, int64_t *hap_len, int64_t *run_start,
+                             int64_t *run_end, int64_t run_cap, int64_t *n_runs, int32_t *bkt, int64_t bkt_cap,
+                             int64_t *n_bkt) {
+  CTX_GUARD(ctx);
+  auto it = ctx->haps.find(slot);
+  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
+  Hap &h = it->second;
+  if (hap_len) *hap_len = h.hap_len;
+  if (n_runs) *n_runs = h.n_runs;
+  if (n_bkt) *n_bkt = h.n_bkt;
+  if (rc && rc_cap < h.hap_len) return arg_fail(ctx, MH_E_CAPACITY, "reverse complement buffer too small");
+  if ((run_start || run_end) && run_cap < h.n_runs) return arg_fail(ctx, MH_E_CAPACITY, "N-run buffers too small");
+  if (bkt && bkt_cap < h.n_bkt + 1) return arg_fail(ctx, MH_E_CAPACITY, "bucket buffer too small");
+  hipStream_t st = ctx->stream;
+  const size_t nr = (size_t)h.n_runs;
+  if (rc && h.hap_len) HIPCHK(ctx, hipMemcpyAsync(rc, h.rc.p, h.hap_len, hipMemcpyDeviceToHost, st));
+  if (run_start && nr) HIPCHK(ctx, hipMemcpyAsync(run_start, h.nrun_s.p, 8 * nr, hipMemcpyDeviceToHost, st));
+  if (run_end && nr) HIPCHK(ctx, hipMemcpyAsync(run_end, h.nrun_e.p, 8 * nr, hipMemcpyDeviceToHost, st));
+  if (bkt) HIPCHK(ctx, hipMemcpyAsync(bkt, h.bkt.p, 4 * (size_t)(h.n_bkt + 1), hipMemcpyDeviceToHost, st));
+  SYNCCHK(ctx, hipStreamSynchronize(st));
+  return MH_OK;
+}
+
 int32_t mh_release_haplotype(mh_ctx *ctx, int32_t slot) {
   CTX_GUARD_NOJOIN(ctx);   // orders itself against queued writers (Hap/TplSet used events)
   auto it = ctx->haps.find(slot);

@@ -53,10 +53,15 @@ class Engine:
     self._vsets[(ri, cpy)] = vset
 
   def _slot(self, key):
-    """A slot for a new build of key: the generation its last slot did not use (that one may still be live)."""
+    """A slot for a new build of key: the generation its last slot did not use (that one may still be live).  Copy
+    cpy of a region owns the slot pair 2 * cpy + {0, 1}, so no two (copy, generation) pairs share a slot."""
+    ri, cpy = key
+    if not 0 <= cpy < self.SLOTS_PER_REGION // 2:
+      raise ValueError('copy {} of region {}: an Engine holds copies 0 .. {} of a region'.format(
+        cpy, ri, self.SLOTS_PER_REGION // 2 - 1))
     g = 1 - self._gen.get(key, 1)
     self._gen[key] = g
-    return key[0] * self.SLOTS_PER_REGION + 2 * g + key[1]
+    return ri * self.SLOTS_PER_REGION + 2 * cpy + g
 
   def haplotype(self, ri, cpy, soa):
     key = (ri, cpy)

@@ -207,6 +207,26 @@ def create_node_list(ref_seq, ref_start_pos, vl):
   return nodes
 
 
+def create_node_list_soa(ref_seq, ref_start_pos, soa):
+  """create_node_list for variants in structure-of-arrays form (pos, op, oplen, alt_off, alt_len, alt_pool): the node
+  arrays (ps, pr, op, oplen, src, seq_off, seq_len) as mo_create_node_list writes them, with no Python tuples.  Node
+  k's bytes are (alt_pool if src[k] else ref_seq)[seq_off[k] : seq_off[k] + seq_len[k]]."""
+  pos = np.ascontiguousarray(soa['pos'], dtype=np.int64)
+  op = np.ascontiguousarray(soa['op'], dtype=np.uint8)
+  oplen = np.ascontiguousarray(soa['oplen'], dtype=np.int64)
+  aoff = np.ascontiguousarray(soa['alt_off'], dtype=np.int64)
+  alen = np.ascontiguousarray(soa['alt_len'], dtype=np.int64)
+  n_var = len(pos)
+  if n_var == 0:
+    pos, op, oplen, aoff, alen = (np.zeros(1, a.dtype) for a in (pos, op, oplen, aoff, alen))
+  cap = 2 * n_var + 1
+  ps, pr, ol, off, sl = (np.empty(cap, np.int64) for _ in range(5))
+  nop, src = np.empty(cap, np.uint8), np.empty(cap, np.uint8)
+  n = lib().mo_create_node_list(ref_seq, len(ref_seq), ref_start_pos, _p(pos), _p(op), _p(oplen), _p(aoff), _p(alen),
+                                n_var, _p(ps), _p(pr), _p(nop), _p(ol), _p(src), _p(off), _p(sl))
+  return ps[:n], pr[:n], nop[:n], ol[:n], src[:n], off[:n], sl[:n]
+
+
 def generate_unit(ref_seq, region_start0, vl, p, rlen, cum_tlen, rng_seed, serial_stub, chrom, cpy):
   pos, op, oplen, aoff, alen, pool = _variant_soa(vl)
   cum_tlen = np.ascontiguousarray(cum_tlen, dtype=np.float64)

@@ -396,6 +396,133 @@ def test_unit_vs_oracle_nine_digit_positions(native, emit_mode):
                          emit_mode=emit_mode) > 10000
 
 
+_NF = {}   # the N-filter tests' contig, variants and oracle results, computed once (read-only)
+
+
+def _n_filter_inputs():
+  """A 200 kbp contig without telomere caps and with an i.i.d. 'N' at one base in 75: a 150-base read holds two 'N's
+  on average, so both outcomes of the reference's rule (readgenerate.py:204: dropped with more than 2) are common,
+  and the haplotype has far more runs than k_emit_measure stages in LDS (MS_RUNS = 128)."""
+  if not _NF:
+    from mitty_amd import synth
+    a = np.frombuffer(synth.contig(200_000, 31, n_gaps=False), dtype=np.uint8).copy()
+    a[np.random.RandomState(32).rand(len(a)) < 1 / 75] = ord('N')
+    _NF['seq'] = a.tobytes()
+    _NF['soa'] = synth.copies_soa(synth.variants(_NF['seq'], 33))[0]
+    _NF['oracle'] = {}
+  return _NF
+
+
+def _n_filter_unit(seq, soa, emit_mode, key, want_runs=None):
+  """One unit on contig seq through the Engine in emit_mode against the oracle (computed once per key); returns
+  (the oracle's kept share of its own templates, the haplotype's N-run count on the device)."""
+  from mitty_amd import _native
+  from mitty_amd.engine import Engine
+  from oracle import oracle as O
+  from tests import splice_ref as R
+  mdl = G.model('hiseq-X-v2.5-Garvan')
+  rlen = int(mdl['mean_rlen'])
+  p, _ = _native.read_model_params(rlen, 30.0)
+  cache = _n_filter_inputs()['oracle']
+  if key not in cache:
+    want = R.Expect(seq, 1, soa)
+    n_tpl = len(O.generate_templates(p, rlen, mdl['cum_tlen'], want.p_min, want.p_max, 77)[0])
+    cache[key] = O.generate_unit_soa(seq, 0, soa, p, rlen, mdl['cum_tlen'], 77, 'NF:0:3', '7', 0) + \
+      (n_tpl, len(want.run_start))
+  k, o1, o2, n_tpl, runs = cache[key]
+  if want_runs is not None:
+    assert runs == want_runs
+  eng = Engine(0, emit_mode)
+  try:
+    eng.load_region(0, ('7', 0, len(seq)), seq)
+    n, kept, b1, b2 = eng.run_unit(3, 0, 0, 77, soa, p, rlen, mdl['cum_tlen'], 'NF')
+    d1, d2 = eng.ctx.fetch_output()
+    dev_runs = len(eng.ctx.get_haplotype_aux(eng._haps[(0, 0)][0])[1])
+  finally:
+    eng.close()
+  print('templates {} kept by the oracle {} ({:.1%}), N runs {}'.format(n_tpl, k, k / n_tpl, runs))
+  assert (n, kept) == (n_tpl, k) and dev_runs == runs
+  G.check_same(d1, o1, 'file 1 differs')
+  G.check_same(d2, o2, 'file 2 differs')
+  return k / n_tpl, dev_runs
+
+
+@pytest.mark.parametrize('emit_mode', [0, 2, 3])
+def test_n_filter_scattered_ns_vs_oracle(native, emit_mode):
+  """Reads with 0 to 5 scattered 'N's: the keep rule's threshold (at most 2) decides about half of the templates,
+  with the N runs searched in global memory (more than MS_RUNS)."""
+  nf = _n_filter_inputs()
+  share, runs = _n_filter_unit(nf['seq'], nf['soa'], emit_mode, 'all')
+  assert 0.25 <= share <= 0.75 and runs > 128
+
+
+@pytest.mark.parametrize('target', [128, 129])
+def test_n_filter_at_ms_runs_vs_oracle(native, target):
+  """The same contig with the surplus 'N's blanked from the end, so the haplotype has exactly MS_RUNS runs (the last
+  count staged in LDS), then one more."""
+  from tests import splice_ref as R
+  nf = _n_filter_inputs()
+  a = np.frombuffer(nf['seq'], dtype=np.uint8)
+  starts, ends = R.n_runs_of(nf['seq'])
+  keep, seq = target, None
+  for _ in range(40):   # (an insertion may split a run and a deletion join two: the haplotype's count decides)
+    b = a.copy()
+    cut = int(ends[keep - 1])
+    b[cut:][b[cut:] == ord('N')] = ord('A')
+    seq = b.tobytes()
+    got = len(R.Expect(seq, 1, nf['soa']).run_start)
+    if got == target:
+      break
+    keep += 1 if got < target else -1
+  else:
+    raise AssertionError('no cut of the contig gives {} runs'.format(target))
+  _, runs = _n_filter_unit(seq, nf['soa'], 0, target, want_runs=target)
+  assert runs == target
+
+
+def test_three_copies_rebuilt_across_steps_vs_oracle(native):
+  """Ploidy 3 with the haplotypes rebuilt: one 300 kbp region, three copies with different variants, two steps of
+  three batches (one copy each) with drop_haplotypes between the steps and the next step's first batch prefetched
+  during the last.  Copy 2's slot and copy 0's second-generation slot are live together; every unit's FASTQ of both
+  steps equals the oracle's."""
+  from mitty_amd import _native, synth
+  from mitty_amd.engine import Engine
+  from oracle import oracle as O
+  mdl = G.model('hiseq-X-v2.5-Garvan')
+  p, passes = _native.read_model_params(150, 10.0)
+  L = 300_000
+  seq = synth.contig(L, 71)
+  copies = [synth.copies_soa(synth.variants(seq, 72 + c))[0] for c in range(3)]
+  assert len({c['pos'].tobytes() for c in copies}) == 3
+  units = _native.work_units(55, [3], passes)
+  job = [(ps, ri, cpy, sd) for ps, (ri, cpy, sd) in enumerate(units)]
+  batches = [[u for u in job if u[2] == c] for c in range(3)]
+  assert all(batches)
+  want = {ps: O.generate_unit_soa(seq, 0, copies[cpy], p, 150, mdl['cum_tlen'], sd, 'P3:0:{}'.format(ps), '9', cpy)
+          for ps, _, cpy, sd in job}
+  eng = Engine(0)
+  try:
+    eng.load_region(0, ('9', 0, L), seq)
+    for c in range(3):
+      eng.upload_variants(0, c, copies[c])
+    for step in range(2):
+      eng.drop_haplotypes()
+      for i, batch in enumerate(batches):
+        last = i + 1 == len(batches)
+        eng.ctx.reset_output()
+        res = eng.run_units(batch, lambda r, c: copies[c], p, 150, mdl['cum_tlen'], 'P3',
+                            prefetch=batches[0] if last else batches[i + 1], prefetch_next_step=last, prefetch_after=0)
+        d1, d2 = eng.ctx.fetch_output()
+        live = [v[0] for v in eng._haps.values()] + [v[0] for v in eng._pre.values()]
+        assert len(set(live)) == len(live)
+        what = 'step {} copy {}'.format(step, i)
+        assert [r[1] for r in res] == [want[u[0]][0] for u in batch], what
+        G.check_same(d1, b''.join(want[u[0]][1] for u in batch), what + ': file 1 differs')
+        G.check_same(d2, b''.join(want[u[0]][2] for u in batch), what + ': file 2 differs')
+  finally:
+    eng.close()
+
+
 def test_batched_units_vs_oracle(native):
   """Several units sampled in one batch (jump-ahead segments for every stream, concurrent decodes, the batch-wide
   permutation sort of mh_sort.h), emitted in the reference's unit order: the arena equals the oracle's per-unit FASTQ

@@ -492,47 +492,96 @@ def test_rpc_variant_helpers_chain_equals_node_list_oracle():
     assert got == want, (vl, got, want)
 
 
+class _SlotCtx:
+  """A stand-in for Context that records Engine's haplotype builds and refuses a build into a live slot."""
+
+  def __init__(self):
+    self.live, self.calls = set(), []
+
+  def build_haplotypes_vset(self, slots, contig_ids, ref_starts, vsets):
+    assert not self.live & set(slots)
+    self.live |= set(slots)
+    self.calls.append(('build', tuple(slots)))
+    return [(3, 1, 9)] * len(slots)
+
+  def prefetch_haplotypes_vset(self, slots, contig_ids, ref_starts, vsets, unit_slots=(), unit_seeds=(), p=1.0):
+    assert not self.live & set(slots)
+    self.live |= set(slots)
+    self.calls.append(('prefetch', tuple(slots)))
+
+  def release_haplotype(self, slot):
+    self.live.remove(slot)
+
+
+def _slot_engine(vsets):
+  from mitty_amd.engine import Engine
+  eng = Engine.__new__(Engine)
+  eng.ctx = _SlotCtx()
+  eng._regions = {0: ('1', 0, 100), 1: ('2', 0, 100)}
+  eng._vsets = dict(vsets)
+  eng._haps, eng._pre, eng._gen = {}, {}, {}
+  return eng
+
+
+def _slots_distinct(eng):
+  """No two live keys (current, or prefetched for the next step) share a slot; the context holds exactly those slots;
+  every slot lies in its region's range."""
+  slots = [v[0] for v in eng._haps.values()] + [v[0] for v in eng._pre.values()]
+  assert len(set(slots)) == len(slots), (eng._haps, eng._pre)
+  assert set(slots) == eng.ctx.live
+  assert all(ri * eng.SLOTS_PER_REGION <= v[0] < (ri + 1) * eng.SLOTS_PER_REGION
+             for d in (eng._haps, eng._pre) for (ri, _), v in d.items())
+
+
 def test_engine_prefetch_slot_generations():
   """Engine's haplotype slots (no GPU: a stand-in context records the calls): a prefetch for the next step builds
   every key afresh into the slot generation its live slot does not use, kept apart until drop_haplotypes releases the
   current ones and adopts them; a prefetch within a step skips keys already built; builds alternate generations, so
-  a key's new slot is never its live one (mh_prefetch_haplotypes_vset refuses live slots)."""
-  from mitty_amd.engine import Engine
-
-  class Ctx:
-    def __init__(self):
-      self.live, self.calls = set(), []
-
-    def build_haplotypes_vset(self, slots, contig_ids, ref_starts, vsets):
-      assert not self.live & set(slots)
-      self.live |= set(slots)
-      self.calls.append(('build', tuple(slots)))
-      return [(3, 1, 9)] * len(slots)
-
-    def prefetch_haplotypes_vset(self, slots, contig_ids, ref_starts, vsets, unit_slots=(), unit_seeds=(), p=1.0):
-      assert not self.live & set(slots)
-      self.live |= set(slots)
-      self.calls.append(('prefetch', tuple(slots)))
-
-    def release_haplotype(self, slot):
-      self.live.remove(slot)
-
-  eng = Engine.__new__(Engine)
-  eng.ctx = Ctx()
-  eng._regions = {0: ('1', 0, 100), 1: ('2', 0, 100)}
-  eng._vsets = {(0, 0): 0, (0, 1): 1, (1, 0): 64, (1, 1): 65}
-  eng._haps, eng._pre, eng._gen = {}, {}, {}
+  a key's new slot is never its live one (mh_prefetch_haplotypes_vset refuses live slots), and no two live keys ever
+  share a slot."""
+  distinct = _slots_distinct
+  eng = _slot_engine({(0, 0): 0, (0, 1): 1, (1, 0): 64, (1, 1): 65})
   a, b = [(0, 0), (0, 1)], [(1, 0), (1, 1)]
   ua, ub = [(0, ri, cpy, 5) for ri, cpy in a], [(0, ri, cpy, 5) for ri, cpy in b]
   eng.haplotypes(a)                        # step 1, batch 0
+  distinct(eng)
   eng.prefetch(ub)                         # batch 1 during batch 0
+  distinct(eng)
   eng.prefetch(ub)                         # (already built: nothing)
   eng.prefetch(ua, next_step=True)         # the next step's batch 0 during the last batch: fresh builds
-  assert eng.ctx.calls == [('build', (0, 1)), ('prefetch', (64, 65)), ('prefetch', (2, 3))]
+  distinct(eng)
+  assert eng.ctx.calls == [('build', (0, 2)), ('prefetch', (64, 66)), ('prefetch', (1, 3))]
   assert set(eng._haps) == set(a + b) and set(eng._pre) == set(a)
   eng.drop_haplotypes()                    # step 2: the prefetched ones become current, the rest released
-  assert eng.ctx.live == {2, 3} and set(eng._haps) == set(a) and not eng._pre
+  distinct(eng)
+  assert eng.ctx.live == {1, 3} and set(eng._haps) == set(a) and not eng._pre
   eng.haplotypes(a + b)                    # a kept (built during step 1), b rebuilt in its other generation
-  assert eng.ctx.calls[-1] == ('build', (66, 67))
+  distinct(eng)
+  assert eng.ctx.calls[-1] == ('build', (65, 67))
   eng.prefetch(ua, next_step=True)
-  assert eng.ctx.calls[-1] == ('prefetch', (0, 1))
+  distinct(eng)
+  assert eng.ctx.calls[-1] == ('prefetch', (0, 2))
+
+
+def test_engine_slots_ploidy3_across_steps():
+  """Three copies of one region, two steps: step 1 touches copies 0-1 only, step 2 all three, so copy 2's first build
+  stands beside copy 0's second generation (with slot = 64 ri + 2 g + cpy both were slot 2: one haplotype silently
+  replaced the other).  Then a next-step prefetch of all three, adopted by drop_haplotypes.  A copy beyond a region's
+  slot range is refused."""
+  from mitty_amd.engine import Engine
+  eng = _slot_engine({(0, c): c for c in range(3)})
+  eng.haplotypes([(0, 0), (0, 1)])
+  _slots_distinct(eng)
+  eng.drop_haplotypes()
+  assert not eng.ctx.live
+  eng.haplotypes([(0, 0), (0, 1), (0, 2)])
+  _slots_distinct(eng)
+  assert len(eng.ctx.live) == 3
+  eng.prefetch([(0, 0, c, 5) for c in range(3)], next_step=True)
+  _slots_distinct(eng)
+  assert len(eng.ctx.live) == 6
+  eng.drop_haplotypes()
+  _slots_distinct(eng)
+  assert set(eng._haps) == {(0, 0), (0, 1), (0, 2)} and len(eng.ctx.live) == 3
+  with pytest.raises(ValueError, match='copies 0 .. 31'):
+    eng._slot((0, Engine.SLOTS_PER_REGION // 2))
