@@ -465,6 +465,12 @@ int32_t mh_bgzf_compress_device(mh_ctx *ctx, const void *d_in, int64_t len, void
                                 int64_t *used);
 int32_t mh_bgzf_compress_gpu(mh_ctx *ctx, const char *in, int64_t len, char *out, int64_t cap, int64_t *used);
 int32_t mh_output_bgzf(mh_ctx *ctx, int32_t file, char *out, int64_t cap, int64_t *used);
+/* Known-answer hook of the device deflate (no reference counterpart: the compressed bytes are this library's own):
+ * mh_bgzf_compress_gpu with the input staged `misalign` bytes (0..15) past a 16-byte boundary, so a test reaches the
+ * byte-wise block staging that BAM windows and odd arena offsets take and compares the members byte for byte with
+ * the host restatement of the parse (tests/deflate_host.cpp --device-rules). */
+int32_t mh_selftest_bgzf(mh_ctx *ctx, const char *in, int64_t len, int32_t misalign, char *out, int64_t cap,
+                         int64_t *used);
 int32_t mh_output_bgzf_range(mh_ctx *ctx, int32_t file, int64_t offset, int64_t len, char *out, int64_t cap,
                              int64_t *used);
 /* Both arenas' bytes [offset, offset + n_f) deflated (file 1, then file 2) with each file's compressed bytes copied

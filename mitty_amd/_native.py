@@ -17,7 +17,7 @@ MH_RNG_MITTY, MH_RNG_PHILOX = 0, 1
 
 # Every exported symbol of include/mitty_hip.h (tests check the library exports all of them).
 EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_error', 'mh_sync',
-           'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort',
+           'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort', 'mh_selftest_bgzf',
            'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes', 'mh_get_haplotype_aux',
            'mh_release_haplotype', 'mh_expand_variant', 'mh_sample_templates', 'mh_sample_templates_span', 'mh_set_templates',
            'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
@@ -76,6 +76,7 @@ def lib():
   _sig(L, 'mh_selftest_scan_fault', [c_vp])
   _sig(L, 'mh_selftest_scan', [c_vp, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_selftest_sort', [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp])
+  _sig(L, 'mh_selftest_bgzf', [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, P_i64])
   _sig(L, 'mh_read_model_params', [c_i64, c_dbl, ctypes.POINTER(c_dbl), P_i64])
   _sig(L, 'mh_work_units', [c_u64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, P_i64])
   _sig(L, 'mh_upload_contig', [c_vp, c_i32, c_vp, c_i64])
@@ -1159,6 +1160,18 @@ class Context:
     self._chk(self._L.mh_selftest_scan(self._h, int(kind), int(fields), _ptr(x), n, int(repeat), _ptr(incl),
                                        _ptr(excl), _ptr(total), _ptr(info)))
     return incl, excl, (total[0] if x.ndim == 1 else total), (int(info[0]), int(info[1]))
+
+  def selftest_bgzf(self, data, misalign=0):
+    """mh_selftest_bgzf: the BGZF members of `data` deflated on the GPU from a source address `misalign` bytes
+    (0..15) past a 16-byte boundary (no EOF marker)."""
+    n = len(data)
+    if n == 0:
+      return b''
+    src = np.frombuffer(data, np.uint8)
+    out = np.empty(n + (n // 0xff00 + 2) * 40 + 64, np.uint8)
+    used = c_i64()
+    self._chk(self._L.mh_selftest_bgzf(self._h, _ptr(src), n, int(misalign), _ptr(out), len(out), ctypes.byref(used)))
+    return out[:used.value].tobytes()
 
   def selftest_scan_fault(self):
     """(return code, message) of mh_selftest_scan_fault: MH_E_STATE when a timed-out look-back scan is reported."""

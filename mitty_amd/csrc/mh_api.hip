@@ -2340,6 +2340,34 @@ int32_t mh_bgzf_compress_gpu(mh_ctx *ctx, const char *in, int64_t len, char *out
   return MH_OK;
 }
 
+// Known-answer hook of the device deflate (mh_deflate.hip): mh_bgzf_compress_gpu with the input placed `misalign`
+// bytes (0..15) past gz_in's 16-byte-aligned start, so a test steers k_bgzf_blocks' byte-wise staging branch (the
+// branch BAM windows and odd arena ranges take) as well as the 16-byte one, and compares the bytes with the host
+// restatement (tests/deflate_host.cpp --device-rules).
+int32_t mh_selftest_bgzf(mh_ctx *ctx, const char *in, int64_t len, int32_t misalign, char *out, int64_t cap,
+                         int64_t *used) {
+  CTX_GUARD(ctx);
+  if ((!in && len > 0) || len < 0 || misalign < 0 || misalign > 15 || !out || !used)
+    return arg_fail(ctx, MH_E_ARG, "bad arguments");
+  *used = 0;
+  if (len == 0) return MH_OK;
+  MH_TRY(gz_drain(ctx));
+  MH_TRY(ensure(ctx, ctx->gz_in, (size_t)len + 16 + 64));
+  MH_TRY(ensure(ctx, ctx->gz_out, (size_t)bgzf_device_bound(len)));
+  const uint8_t *src = (const uint8_t *)ctx->gz_in.p + misalign;
+  HIPCHK(ctx, hipMemcpyAsync((void *)src, in, len, hipMemcpyHostToDevice, ctx->stream));
+  int64_t u = 0;
+  MH_TRY(bgzf_device(ctx, ctx->stream, src, len, (uint8_t *)ctx->gz_out.p, (int64_t)ctx->gz_out.cap, &u));
+  if (u > cap) {
+    *used = u;
+    return arg_fail(ctx, MH_E_CAPACITY, "output buffer too small");
+  }
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->gz_out.p, u, hipMemcpyDeviceToHost, ctx->stream));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *used = u;
+  return MH_OK;
+}
+
 int32_t mh_output_bgzf_range(mh_ctx *ctx, int32_t file, int64_t offset, int64_t len, char *out, int64_t cap,
                              int64_t *used) {
   CTX_GUARD(ctx);

@@ -1811,18 +1811,7 @@ def test_philox_sampling_properties(native):
 
 
 # ---- device BGZF (mh_deflate.hip) ----------------------------------------------------------
-def _bgzf_members(z):
-  """The BGZF members of z: (BSIZE, ISIZE) each, checking the gzip header and the BC extra field."""
-  out, o = [], 0
-  while o < len(z):
-    assert z[o:o + 4] == b'\x1f\x8b\x08\x04' and z[o + 12:o + 16] == b'BC\x02\x00', o
-    bsize = int.from_bytes(z[o + 16:o + 18], 'little') + 1
-    isize = int.from_bytes(z[o + bsize - 4:o + bsize], 'little')
-    assert isize <= 0xff00
-    out.append((bsize, isize))
-    o += bsize
-  assert o == len(z)
-  return out
+from tests.deflate_cases import bgzf_members as _bgzf_members   # (shared with tests/test_gpu_deflate.py)
 
 
 @pytest.mark.parametrize('name', ['fastq', 'random', 'zeros', 'one', 'block', 'block1', 'large', 'mixed', 'chunked'])
