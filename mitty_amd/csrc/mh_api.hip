@@ -1248,11 +1248,20 @@ int32_t mh_templates_import(mh_ctx *ctx, int32_t tpl_id, int32_t on_device, cons
     HIPCHK(ctx, hipMemcpyAsync(ts.pos1.p, pos1, 8 * n, k, ctx->stream));
   }
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (ts.prep.valid) ctx->eset[ts.prep.set].prepared = false;   // the buffer set of a measure pass made for the old set
-  ts.prep.valid = false;
+  prep_drop(ctx, ts);   // (a measure pass made for the old set)
   ts.n = n;
   ts.rlen = rlen;
   ts.valid = true;
+  return MH_OK;
+}
+
+// The haplotype an emission entry point reads.  A slot whose splice the prefetch thread still issues is joined first
+// (its splice was queued on the prefetch stream; the thread clears and sets `valid`, so the flag is read after the join)
+static int32_t emit_hap(mh_ctx *ctx, int32_t slot, const Hap **hap) {
+  auto it = ctx->haps.find(slot);
+  if (it != ctx->haps.end() && it->second.prefetched) MH_TRY(join_prefetch(ctx));
+  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
+  *hap = &it->second;
   return MH_OK;
 }
 
@@ -1260,11 +1269,10 @@ int32_t mh_emit_reads(mh_ctx *ctx, int32_t slot, const char *serial_stub, const 
                       int32_t write_fastq2, uint64_t unit_key, int64_t *out_kept, int64_t *out_b1, int64_t *out_b2) {
   CTX_GUARD_EMIT(ctx);
   MH_TRY(lazy_resolve(ctx));   // (appends at the arenas' exact ends)
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
-  if (it->second.prefetched) MH_TRY(join_prefetch(ctx));   // (its splice was queued on the prefetch stream)
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!serial_stub || !chrom || !out_kept || !out_b1 || !out_b2) return arg_fail(ctx, MH_E_ARG, "null argument");
-  return emit_reads(ctx, it->second, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, false, out_kept,
+  return emit_reads(ctx, *hap, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, false, out_kept,
                     out_b1, out_b2);
 }
 
@@ -1272,12 +1280,11 @@ int32_t mh_emit_prepare(mh_ctx *ctx, int32_t slot, const char *serial_stub, cons
                         int32_t write_fastq2, uint64_t unit_key, int64_t *out_kept, int64_t *out_b1, int64_t *out_b2) {
   CTX_GUARD_EMIT(ctx);
   MH_TRY(lazy_resolve(ctx));   // (appends at the arenas' exact ends)
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
-  if (it->second.prefetched) MH_TRY(join_prefetch(ctx));   // (its splice was queued on the prefetch stream)
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!serial_stub || !chrom || (!out_kept) != (!out_b1) || (!out_kept) != (!out_b2))
     return arg_fail(ctx, MH_E_ARG, "null argument");
-  return emit_reads(ctx, it->second, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, true, out_kept,
+  return emit_reads(ctx, *hap, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, true, out_kept,
                     out_b1, out_b2);
 }
 
@@ -1286,30 +1293,28 @@ int32_t mh_emit_reads_range(mh_ctx *ctx, int32_t slot, const char *serial_stub, 
                             int64_t cnt_base, int64_t *out_kept, int64_t *out_b1, int64_t *out_b2) {
   CTX_GUARD_EMIT(ctx);
   MH_TRY(lazy_resolve(ctx));   // (appends at the arenas' exact ends)
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
-  if (it->second.prefetched) MH_TRY(join_prefetch(ctx));   // (its splice was queued on the prefetch stream)
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!serial_stub || !chrom || !out_kept || !out_b1 || !out_b2) return arg_fail(ctx, MH_E_ARG, "null argument");
   if (t_begin < 0 || t_end < t_begin || cnt_base < 0) return arg_fail(ctx, MH_E_ARG, "bad template range");
-  return emit_reads(ctx, it->second, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, t_begin, t_end, cnt_base,
+  return emit_reads(ctx, *hap, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, t_begin, t_end, cnt_base,
                     false, out_kept, out_b1, out_b2);
 }
 
 int32_t mh_emit_reads_async(mh_ctx *ctx, int32_t slot, const char *serial_stub, const char *chrom, int64_t cpy,
                             int32_t write_fastq2, uint64_t unit_key) {
   CTX_GUARD_EMIT(ctx);
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
-  if (it->second.prefetched) MH_TRY(join_prefetch(ctx));   // (its splice was queued on the prefetch stream)
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!serial_stub || !chrom) return arg_fail(ctx, MH_E_ARG, "null argument");
   bool queued = false;
-  MH_TRY(emit_unit_async(ctx, it->second, serial_stub, chrom, cpy, write_fastq2, unit_key, &queued));
+  MH_TRY(emit_unit_async(ctx, *hap, serial_stub, chrom, cpy, write_fastq2, unit_key, &queued));
   if (queued) return MH_OK;
   // a unit the single-pass writer does not cover: the two-pass path at the arenas' exact ends, its totals queued
   // in order with the others
   MH_TRY(lazy_resolve(ctx));
   int64_t k = 0, b1 = 0, b2 = 0;
-  MH_TRY(emit_reads(ctx, it->second, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, false, &k, &b1,
+  MH_TRY(emit_reads(ctx, *hap, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, 0, -1, 0, false, &k, &b1,
                     &b2));
   ctx->lazy.push_back(mh_ctx::LazyUnit{-1, ctx->lazy_gen, {k, b1, b2}});
   return MH_OK;
@@ -1332,28 +1337,24 @@ int32_t mh_emit_measure(mh_ctx *ctx, int32_t slot, const char *serial_stub, cons
                         int32_t write_fastq2, uint64_t unit_key, int64_t t_begin, int64_t t_end, int64_t cnt_base,
                         int64_t *out_kept, int64_t *out_b1, int64_t *out_b2) {
   CTX_GUARD_EMIT(ctx);
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
-  if (it->second.prefetched) MH_TRY(join_prefetch(ctx));   // (its splice was queued on the prefetch stream)
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!serial_stub || !chrom || !out_kept || !out_b1 || !out_b2) return arg_fail(ctx, MH_E_ARG, "null argument");
   if (t_begin < 0 || (t_end >= 0 && t_end < t_begin) || cnt_base < 0) return arg_fail(ctx, MH_E_ARG, "bad template range");
-  MH_TRY(emit_reads(ctx, it->second, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, t_begin, t_end, cnt_base,
+  MH_TRY(emit_reads(ctx, *hap, slot, serial_stub, chrom, cpy, write_fastq2, unit_key, t_begin, t_end, cnt_base,
                     true, out_kept, out_b1, out_b2));
-  auto tit = ctx->tsets.find(ctx->cur_tpl);   // the preparation is dropped: its buffer set is free again
-  if (tit != ctx->tsets.end() && tit->second.prep.valid) {
-    ctx->eset[tit->second.prep.set].prepared = false;
-    tit->second.prep.valid = false;
-  }
+  auto tit = ctx->tsets.find(ctx->cur_tpl);
+  if (tit != ctx->tsets.end()) prep_drop(ctx, tit->second);   // (measured only: its buffer set is free again)
   return MH_OK;
 }
 
 int32_t mh_count_kept(mh_ctx *ctx, int32_t slot, int64_t t_begin, int64_t t_end, int64_t *out_kept) {
   CTX_GUARD(ctx);
-  auto it = ctx->haps.find(slot);
-  if (it == ctx->haps.end() || !it->second.valid) return arg_fail(ctx, MH_E_STATE, "empty haplotype slot");
+  const Hap *hap = nullptr;
+  MH_TRY(emit_hap(ctx, slot, &hap));
   if (!out_kept) return arg_fail(ctx, MH_E_ARG, "null argument");
   if (t_begin < 0 || t_end < t_begin) return arg_fail(ctx, MH_E_ARG, "bad template range");
-  return count_kept(ctx, it->second, t_begin, t_end, out_kept);
+  return count_kept(ctx, *hap, t_begin, t_end, out_kept);
 }
 
 int32_t mh_output_size(mh_ctx *ctx, int64_t *b1, int64_t *b2) {

@@ -1774,9 +1774,6 @@ __device__ __forceinline__ void cr_block_fast(const uint8_t *bkf, const uint16_t
 __device__ __forceinline__ uint32_t cr_block_codes(uint32_t ps, const uint32_t *RW, const CorruptCfg &cc, uint2 key,
                                                    uint32_t tl, uint32_t th, int f, int n0) {
   uint32_t cd = 0;
-#ifdef EW_CALIB_NOPS
-  ps = 0;
-#endif
   while (ps) {
     const int j = __builtin_ctz(ps);
     ps &= ps - 1;
@@ -1865,9 +1862,6 @@ __global__ void __launch_bounds__(CC_THREADS) __attribute__((amdgpu_waves_per_eu
       cr_block_fast(bkf, fp16, cc, key, tl, th, f, n0, qd, &ps, &px, RW);
       code = cr_block_codes(ps, RW, cc, key, tl, th, f, n0);   // the fast bases' codes (RW dies here)
       if (!act) px = 0;
-#ifdef EW_CALIB_NOPX
-      px = 0;
-#endif
       if (__ballot(px != 0)) {   // wave-uniform
         // list the wave's flagged (lane, base) items
         int total = 0;
@@ -1977,13 +1971,12 @@ static int32_t launch_cr_rows(mh_ctx *ctx, hipStream_t st, int64_t m, int32_t nf
   const int64_t NB = (rlen + CI_BLK - 1) / CI_BLK;
   if (m * nf * NB >= ((int64_t)1 << 31)) return arg_fail(ctx, MH_E_STATE, "corruption rows: bad shape");
   CiArgs A{0, 0, m, nullptr, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr}, nullptr, rlen, nf, 0, cc};
-  stage_begin(ctx, "emit_corrupt_rows");
+  StageScope stage(ctx, "emit_corrupt_rows");
   const size_t lds_c = cc_tables_lds(cc.n_bq) + CC_WAVES * sizeof(CcWave);
   const int64_t gx = (m + CC_PER_WG - 1) / CC_PER_WG;
   if (gx >= INT32_MAX || nf * NB > 65535) return arg_fail(ctx, MH_E_CAPACITY, "corruption rows: grid");
   hipLaunchKernelGGL(k_cr_cols, dim3((unsigned)gx, (unsigned)(nf * NB)), dim3(CC_THREADS), lds_c, st, A, rows, codes);
   HIPCHK(ctx, hipGetLastError());
-  stage_end(ctx);
   return MH_OK;
 }
 
@@ -2034,7 +2027,7 @@ int32_t launch_cr_inplace(mh_ctx *ctx, hipStream_t st, const HapView &hv, int64_
   if (grid < 1) grid = 1;
   if (pf) grid = (grid + 1) & ~(int64_t)1;   // even: workgroup pairs (file 0, file 1)
   CiArgs A{hv.p_min, hv.hap_len, m, pos0, pos1, fo0, recs, off, {o1, o2}, crec, rlen, nf, lh0, cc};
-  stage_begin(ctx, "emit_corrupt");
+  StageScope stage(ctx, "emit_corrupt");
   if (!crec_ready) {   // (the fused writer wrote the record words itself)
     hipLaunchKernelGGL(k_cr_recs, dim3(grid_for(m, 256, INT32_MAX)), dim3(256), 0, st, A, crec);
     HIPCHK(ctx, hipGetLastError());
@@ -2046,7 +2039,6 @@ int32_t launch_cr_inplace(mh_ctx *ctx, hipStream_t st, const HapView &hv, int64_
   else
     hipLaunchKernelGGL((k_cr_inplace<false, false, CI_THREADS>), dim3((unsigned)grid), dim3(CI_THREADS), 0, st, A);
   HIPCHK(ctx, hipGetLastError());
-  stage_end(ctx);
   return MH_OK;
 }
 
@@ -2100,11 +2092,19 @@ extern "C" int mh_ew_prof(unsigned long long *out) {   // the sums since the las
 #endif
 
 
-int32_t count_kept(mh_ctx *ctx, const Hap &h, int64_t t_begin, int64_t t_end, int64_t *out_kept) {
+// the current template set (mh_sample_templates / mh_use_templates)
+static int32_t cur_templates(mh_ctx *ctx, const TplSet **tp) {
   auto tit = ctx->tsets.find(ctx->cur_tpl);
   if (tit == ctx->tsets.end() || !tit->second.valid)
     return arg_fail(ctx, MH_E_STATE, "no templates: call mh_sample_templates / mh_use_templates first");
-  const TplSet &tp = tit->second;
+  *tp = &tit->second;
+  return MH_OK;
+}
+
+int32_t count_kept(mh_ctx *ctx, const Hap &h, int64_t t_begin, int64_t t_end, int64_t *out_kept) {
+  const TplSet *tpp = nullptr;
+  MH_TRY(cur_templates(ctx, &tpp));
+  const TplSet &tp = *tpp;
   if (t_end > tp.n) t_end = tp.n;
   *out_kept = 0;
   if (t_begin >= t_end) return MH_OK;
@@ -2121,29 +2121,38 @@ int32_t count_kept(mh_ctx *ctx, const Hap &h, int64_t t_begin, int64_t t_end, in
   return MH_OK;
 }
 
+static int32_t ndig_host(int64_t v) {
+  int32_t d = 1;
+  for (; v >= 10; v /= 10) d++;
+  return d;
+}
 // Sum of digits(c) for c = 1..K (host side of digit_sum)
 static int64_t digit_sum_host(int64_t K) {
   if (K <= 0) return 0;
-  int nd = 1;
-  for (int64_t v = K; v >= 10; v /= 10) nd++;
+  const int nd = ndig_host(K);
   int64_t rep = 0;
   for (int i = 0; i < nd; i++) rep = rep * 10 + 1;
   return (K + 1) * nd - rep;
 }
 
-// dynamic LDS of k_emit_tiles: metadata, windows, qname buffers, T, seam chunks, dump
-// qname rows: a multiple of 16 bytes plus 4 (an odd number of dwords), so wave 0's lanes (one qname row per template)
-// writing the same column land on 32 different LDS banks instead of 8
-constexpr int32_t ED_QPAD = 4;
-// the direct writer's instantiation: CR mode (0 perfect, 1 in-place corruption after it, 2 corruption rows), one or
-// two files
+// ---- the direct writer's host side: one plan, one buffer-set acquisition, one launch sequence, shared by the
+// readback path (emit_reads) and the chained one (emit_unit_async) ----------------------------------------------------
+// the direct writer's instantiation: the single-pass writer (k_emit_fused) or the two-pass one (k_emit_tiles), CR mode
+// (0 perfect, 1 in-place corruption after it, 2 corruption rows), one or two files
 using EwKernel = void (*)(TArgs, QHead);
-static EwKernel ew_kernel(int cr, bool two) {
+static EwKernel ew_kernel(bool single, int cr, bool two) {
+  if (single)   // (no CR 1: a unit with in-place corruption takes the two-pass path)
+    return cr == 2 ? (two ? k_emit_fused<2, 4, 2, 3> : k_emit_fused<1, 8, 2, 3>)
+                   : (two ? k_emit_fused<2, 4, 0, 3> : k_emit_fused<1, 8, 0, 3>);
   return cr == 2 ? (two ? k_emit_tiles<2, 4, 2, 3> : k_emit_tiles<1, 8, 2, 3>)
          : cr == 1 ? (two ? k_emit_tiles<2, 4, 1, 3> : k_emit_tiles<1, 8, 1, 3>)
                    : (two ? k_emit_tiles<2, 4, 0, 3> : k_emit_tiles<1, 8, 0, 3>);
 }
 
+// qname rows: a multiple of 16 bytes plus 4 (an odd number of dwords), so wave 0's lanes (one qname row per template)
+// writing the same column land on 32 different LDS banks instead of 8
+constexpr int32_t ED_QPAD = 4;
+// dynamic LDS of k_emit_tiles: metadata, windows, qname buffers, T, seam chunks, dump
 static size_t ed_lds_bytes(int32_t win_stride, int32_t qstride, int64_t rlen, int nf, bool rows) {
   const bool staged = !rows;   // (rows: the seam chunks stored by the seam pass, no LDS for them)
   const size_t TS = (size_t)((rlen + 4 + 15) / 16 * 16);   // CR 2: a T per record (emit_tile)
@@ -2152,13 +2161,157 @@ static size_t ed_lds_bytes(int32_t win_stride, int32_t qstride, int64_t rlen, in
          (staged ? (size_t)nf * ED_T * 4 * 16 : 0) + 16 + (rows ? ED_PAD + (size_t)nf * ED_T * TS + 16 : 0);
 }
 
+// What the direct writer of one unit is launched with: the qname's fixed parts, the LDS layout, the corruption mode.
+struct WriterPlan {
+  int64_t rlen = 0;
+  int32_t nf = 1, win_stride = 0, head = 0;
+  int32_t hrow = 0, qstride = 0;   // qname buffer per template (emit_tile): head room, then the reads part (hrow)
+  size_t lds_d = 0;
+  int cr = 0;                      // corruption: 0 none, 1 in place after the writer, 2 rows before it
+  QHead qh{};                      // prefix + mid by value (filled when they fit)
+  std::string prefix, mid;         // '@stub:' and '|chrom|cpy'
+  bool head_fits = false;
+  bool direct_ok = false;          // the head fits QHead, the windows the writer's groups, the layout 64 KiB of LDS
+  // the rows for `hslot`, the longest reads part + '\n' of the unit
+  void size_rows(int32_t hslot) {
+    hrow = hslot > 16 ? (hslot + 15) / 16 * 16 : 16;
+    qstride = head + hrow + 32 + ED_QPAD;
+    lds_d = ed_lds_bytes(win_stride, qstride, rlen, nf, cr == 2);
+    direct_ok = head_fits && win_stride <= 16 * 3 * ED_GMAX && lds_d <= 64 * 1024;
+  }
+};
+// hslot: from the measure pass's maxima (emit_reads, which plans before it and sizes the rows after) or the splice's
+// bound (emit_unit_async)
+static WriterPlan writer_plan(const mh_ctx *ctx, int64_t rlen, const char *serial_stub, const char *chrom, int64_t cpy,
+                              int32_t write_fastq2, int32_t hslot) {
+  WriterPlan P;
+  P.rlen = rlen;
+  P.nf = write_fastq2 ? 2 : 1;
+  P.prefix = std::string("@") + serial_stub + ":";
+  P.mid = std::string("|") + chrom + "|" + std::to_string(cpy);
+  P.win_stride = (int32_t)(((rlen + 31) / 16) * 16);
+  P.head = (int32_t)(((P.prefix.size() + P.mid.size() + 10 + 16) + 15) / 16 * 16);
+  P.cr = !ctx->corrupt_on ? 0 : cr_rows_lds(P.nf, rlen, ctx->corrupt_n_bq) ? 2 : 1;
+  QHead &qh = P.qh;
+  P.head_fits = P.prefix.size() + P.mid.size() <= sizeof(qh.w);
+  P.size_rows(hslot);
+  if (P.head_fits) {
+    const std::string pm = P.prefix + P.mid;
+    std::memcpy(qh.w, pm.data(), pm.size());
+    qh.lp = (int32_t)P.prefix.size();
+    qh.lm = (int32_t)P.mid.size();
+  }
+  return P;
+}
+
+// The next buffer set in rotation for a unit of m templates, every set sized for the most templates a unit had, and
+// the main stream's scan scratch for `nscan` items.  All of a unit's allocation happens here and in its caller, before
+// the unit's first stream operation: a reallocation may drain the writers, nothing after it does.
+static int32_t eset_reserve(mh_ctx *ctx, int64_t m, int64_t nscan, int32_t *set) {
+  *set = ctx->eset_i;
+  EmitSet &es = ctx->eset[*set];
+  ctx->eset_i = (ctx->eset_i + 1) % mh_ctx::N_ESET;
+  if (m > ctx->eset_max_m) ctx->eset_max_m = m;
+  const int64_t mm = ctx->eset_max_m, mt = (mm + ED_T - 1) / ED_T;
+  MH_TRY(ensure(ctx, es.recs, sizeof(Rec) * mm));
+  MH_TRY(ensure(ctx, es.tsum, sizeof(int4) * (size_t)mt));
+  MH_TRY(ensure(ctx, es.tpre, sizeof(E3) * (size_t)mt));
+  MH_TRY(ensure(ctx, es.stat, 64));
+  return ensure(ctx, ctx->scan_partials, scan_lb_scratch_bytes<E3>(nscan));
+}
+
+// The measure pass of templates [t_begin, t_begin + m) into `es` on the main stream, after the writer that last read
+// the set (N_ESET units ago), then (tiles) the tile scan: per-tile prefixes in es.tpre, the totals at es.stat + 0
+static int32_t queue_measure(mh_ctx *ctx, EmitSet &es, const HapView &hv, const TplSet &tp, int64_t t_begin, int64_t m,
+                             const QFixed &q, bool tiles) {
+  hipStream_t st = ctx->stream;
+  if (es.busy) HIPCHK(ctx, hipStreamWaitEvent(st, es.done, 0));
+  char *stat = (char *)es.stat.p;   // the totals (E3) at [0, 24), the maxima at [32, 48)
+  {
+    StageScope stage(ctx, "emit_measure");
+    hipLaunchKernelGGL(k_emit_measure, dim3(grid_for(m, 256, INT32_MAX)), dim3(256), 0, st, hv, m,
+                       (const int64_t *)tp.pos0.p + t_begin, (const int64_t *)tp.pos1.p + t_begin,
+                       (const int8_t *)tp.fo0.p + t_begin, (int64_t)tp.rlen, q, (int32_t)ctx->corrupt_on,
+                       (Rec *)es.recs.p, (int4 *)es.tsum.p, (int32_t *)(stat + 32),
+                       tp.has_n0 ? (const int32_t *)tp.n0.p + t_begin : nullptr);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  if (!tiles) return MH_OK;
+  const int64_t ntiles = (m + ED_T - 1) / ED_T;
+  StageScope stage(ctx, "emit_scan");
+  HIPCHK(ctx, device_scan_sum<E3>(st, ntiles, LoadTile{(const int4 *)es.tsum.p, ntiles}, StoreTile{(E3 *)es.tpre.p},
+                                  ctx->scan_partials.p, (E3 *)stat));
+  return MH_OK;
+}
+
+// The direct writer's arguments for templates [t_begin, t_begin + m); the chain's fields (lb .. hcap) stay zero
+static TArgs writer_args(const mh_ctx *ctx, const WriterPlan &P, const HapView &hv, const TplSet &tp, int64_t t_begin,
+                         int64_t m, int64_t cnt_base, const EmitSet *es) {
+  TArgs A{};
+  A.h = hv;
+  A.m = m;
+  A.pos0 = (const int64_t *)tp.pos0.p + t_begin;
+  A.pos1 = (const int64_t *)tp.pos1.p + t_begin;
+  A.fo0 = (const int8_t *)tp.fo0.p + t_begin;
+  if (es) {
+    A.recs = (const Rec *)es->recs.p;
+    A.tpre = (const E3 *)es->tpre.p;
+  }
+  A.arena[0] = (char *)ctx->out1.p;
+  A.arena[1] = (char *)ctx->out2.p;
+  A.used[0] = ctx->used1;
+  A.used[1] = ctx->used2;
+  A.cnt_base = cnt_base;
+  A.rlen = (int32_t)P.rlen;
+  A.win_stride = P.win_stride;
+  A.head = P.head;
+  A.qstride = P.qstride;
+  return A;
+}
+
+// The direct writer of one unit queued on the writer stream, after `dep` on the main stream (null: everything queued
+// there so far): the row pass (P.cr 2), the writer (single: k_emit_fused), the in-place pass (P.cr 1).  `es`: the
+// unit's buffer set (none for the single-pass writer); `emit`: the caller's "emit" stage, ended on the writer stream.
+// The call returns while the writer runs, so the next unit's measure pass and the next job's sampling overlap it.
+static int32_t queue_writer(mh_ctx *ctx, const WriterPlan &P, TArgs &A, bool single, const CorruptCfg &cc,
+                            hipEvent_t dep, EmitSet *es, const Hap &h, const TplSet &tp, StageScope &emit) {
+  hipStream_t ws = ctx->wstream;
+  if (!dep) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_ready, ctx->stream));
+    dep = ctx->ev_ready;
+  }
+  HIPCHK(ctx, hipStreamWaitEvent(ws, dep, 0));
+  {
+    StageStreamScope on_ws(ctx, ws);
+    if (P.cr == 2) MH_TRY(cr_rows_prepare(ctx, ws, A.m, P.nf, A.rlen, cc, A));
+    {
+      StageScope stage(ctx, "emit_write");   // (after the row pass: the stage times the writer alone)
+      hipLaunchKernelGGL(ew_kernel(single, P.cr, P.nf == 2), dim3((unsigned)((A.m + ED_T - 1) / ED_T)),
+                         dim3(ED_THREADS), P.lds_d, ws, A, P.qh);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    if (P.cr == 1)   // (tables too large for the row pass's LDS): in place after the writer
+      MH_TRY(launch_cr_inplace(ctx, ws, A.h, A.m, A.pos0, A.pos1, A.fo0, A.recs, nullptr, A.crec, A.arena[0],
+                               A.arena[1], P.nf, (int32_t)(P.prefix.size() + P.mid.size()), A.rlen, cc, true));
+    emit.end();
+  }
+  if (es) {
+    HIPCHK(ctx, hipEventRecord(es->done, ws));
+    es->busy = true;
+  }
+  HIPCHK(ctx, hipEventRecord(ctx->ev_writer, ws));
+  MH_TRY(mark_used(ctx, h.used, h.used_set));     // the haplotype and the templates stay live until then
+  MH_TRY(mark_used(ctx, tp.used, tp.used_set));
+  ctx->writer_pending = true;
+  return MH_OK;
+}
+
 int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_stub, const char *chrom, int64_t cpy,
                    int32_t write_fastq2, uint64_t unit_key, int64_t t_begin, int64_t t_end, int64_t cnt_base,
                    bool prepare_only, int64_t *out_kept, int64_t *out_b1, int64_t *out_b2) {
-  auto tit = ctx->tsets.find(ctx->cur_tpl);
-  if (tit == ctx->tsets.end() || !tit->second.valid)
-    return arg_fail(ctx, MH_E_STATE, "no templates: call mh_sample_templates / mh_use_templates first");
-  const TplSet &tp = tit->second;
+  const TplSet *tpp = nullptr;
+  MH_TRY(cur_templates(ctx, &tpp));
+  const TplSet &tp = *tpp;
   hipStream_t st = ctx->stream;
   if (t_end < 0 || t_end > tp.n) t_end = tp.n;
   if (t_begin > t_end) t_begin = t_end;
@@ -2166,8 +2319,9 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
   const int64_t *pos0 = (const int64_t *)tp.pos0.p + t_begin, *pos1 = (const int64_t *)tp.pos1.p + t_begin;
   const int8_t *fo0 = (const int8_t *)tp.fo0.p + t_begin;
   const int64_t rlen = tp.rlen;
-  std::string prefix = std::string("@") + serial_stub + ":";
-  std::string mid = std::string("|") + chrom + "|" + std::to_string(cpy);
+  // (the qname rows sized below, once the measure pass's maxima are known)
+  WriterPlan P = writer_plan(ctx, rlen, serial_stub, chrom, cpy, write_fastq2, 0);
+  const std::string &prefix = P.prefix, &mid = P.mid;
   if (prefix.size() + mid.size() > 4000) return arg_fail(ctx, MH_E_ARG, "sample/chrom names too long");
   // prepare_only with null outputs: return without waiting for the measure pass (its totals are read back when the
   // unit's writer is queued), so a batch's measure passes run back to back with no host round trip between them
@@ -2194,10 +2348,7 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
   EmitPrep &pp = tp.prep;
   const bool have_prep = !prepare_only && pp.valid && pp.slot == slot && pp.t_begin == t_begin && pp.t_end == t_end &&
                          pp.cnt_base == cnt_base && pp.prefix == prefix && pp.mid == mid && pp.direct == direct;
-  if (pp.valid && !have_prep) {   // a stale preparation: its buffer set is free again
-    ctx->eset[pp.set].prepared = false;
-    pp.valid = false;
-  }
+  if (!have_prep) prep_drop(ctx, tp);   // (a stale preparation)
   int32_t set;
   E3 ht;
   int32_t hm4[4] = {0, 0, 0, 0};   // max record length + 20, -, -, longest reads part + '\n'
@@ -2206,7 +2357,7 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
     const int64_t ds = digit_sum_host(cnt_base + t.kept) - digit_sum_host(cnt_base);
     return E3{t.kept, t.b1 + ds, t.b2 + ds};
   };
-  stage_begin(ctx, "emit");
+  StageScope emit(ctx, "emit");
   // what the writer waits for on the main stream: everything queued there so far, or (a deferred preparation) only
   // this unit's measure pass and tile scan — not the measure passes of the units prepared after it
   hipEvent_t writer_dep = nullptr;
@@ -2226,44 +2377,20 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
     }
     pp.valid = false;
   } else {
-    // this unit's buffer set; the writer that last read it (N_ESET units ago) must be done before the measure
-    // refills it
-    set = ctx->eset_i;
-    EmitSet &es = ctx->eset[set];
-    if (es.prepared) {
-      stage_end(ctx);
+    if (ctx->eset[ctx->eset_i].prepared)
       return arg_fail(ctx, MH_E_STATE, "more units prepared than emission buffer sets (emit the prepared units first)");
-    }
-    ctx->eset_i = (ctx->eset_i + 1) % mh_ctx::N_ESET;
-    if (es.busy) HIPCHK(ctx, hipStreamWaitEvent(st, es.done, 0));
-    if (m > ctx->eset_max_m) ctx->eset_max_m = m;
-    const int64_t mm = ctx->eset_max_m, mt = (mm + ED_T - 1) / ED_T;
-    MH_TRY(ensure(ctx, es.recs, sizeof(Rec) * mm));
-    MH_TRY(ensure(ctx, es.tsum, sizeof(int4) * (size_t)mt));
-    MH_TRY(ensure(ctx, es.tpre, sizeof(E3) * (size_t)mt));
+    MH_TRY(eset_reserve(ctx, m, direct ? ntiles : m + 1, &set));
+    EmitSet &es = ctx->eset[set];
     if (!direct) MH_TRY(ensure(ctx, es.off, sizeof(E3) * (m + 1)));
     if (ctx->corrupt_on) MH_TRY(ensure(ctx, es.crrec, 16 * (size_t)m + 64));   // 8 bytes per record
-    MH_TRY(ensure(ctx, ctx->scan_partials, scan_lb_scratch_bytes<E3>(direct ? ntiles : m + 1)));
-    MH_TRY(ensure(ctx, es.stat, 64));
     char *stat = (char *)es.stat.p;        // per set: a deferred readback must not see the next unit's totals
-    E3 *tot = (E3 *)stat;                  // [0, 24)
-    int32_t *max_rec = (int32_t *)(stat + 32);   // [32, 48); the overflow area's fill at 48
-    HIPCHK(ctx, hipMemsetAsync(stat, 0, 64, st));
-    Rec *recs = (Rec *)es.recs.p;
-    stage_begin(ctx, "emit_measure");
-    hipLaunchKernelGGL(k_emit_measure, dim3(grid_for(m, 256, INT32_MAX)), dim3(256), 0, st, hv, m, pos0, pos1, fo0,
-                       rlen, q, (int32_t)ctx->corrupt_on, recs, (int4 *)es.tsum.p, max_rec,
-                       tp.has_n0 ? (const int32_t *)tp.n0.p + t_begin : nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
-    stage_begin(ctx, "emit_scan");
-    if (direct)
-      HIPCHK(ctx, device_scan_sum<E3>(st, ntiles, LoadTile{(const int4 *)es.tsum.p, ntiles},
-                                      StoreTile{(E3 *)es.tpre.p}, ctx->scan_partials.p, tot));
-    else
-      HIPCHK(ctx, device_scan_sum<E3>(st, m + 1, LoadRec{recs, m}, StoreOff{(E3 *)es.off.p, cnt_base},
-                                      ctx->scan_partials.p, tot));
-    stage_end(ctx);
+    HIPCHK(ctx, hipMemsetAsync(stat, 0, 64, st));   // (the maxima at [32, 48) are read back here)
+    MH_TRY(queue_measure(ctx, es, hv, tp, t_begin, m, q, direct));
+    if (!direct) {   // the LDS-image writer reads per-template offsets
+      StageScope stage(ctx, "emit_scan");
+      HIPCHK(ctx, device_scan_sum<E3>(st, m + 1, LoadRec{(const Rec *)es.recs.p, m},
+                                      StoreOff{(E3 *)es.off.p, cnt_base}, ctx->scan_partials.p, (E3 *)stat));
+    }
     if (defer) {
       // the totals (stat + 0) and the maxima (stat + 32) in one copy: a small copy costs a blit launch
       HIPCHK(ctx, hipMemcpyAsync(es.h_stat, stat, 48, hipMemcpyDeviceToHost, st));
@@ -2278,7 +2405,6 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
       ht = totals(ht);
     }
     if (prepare_only) {
-      stage_end(ctx);
       pp.valid = true;
       pp.set = set;
       pp.slot = slot;
@@ -2313,77 +2439,26 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
 
   int32_t cap = 16 * 1024;
   while (cap < hmax) cap *= 2;
-  if (cap > 64 * 1024) {
-    stage_end(ctx);
-    return arg_fail(ctx, MH_E_CAPACITY, "a FASTQ record exceeds 64 KiB");
-  }
-  const int32_t win_stride = (int32_t)(((rlen + 31) / 16) * 16);
-  size_t lds = ((sizeof(TplMeta) * EW_T + 15) / 16) * 16 + (size_t)EW_T * 2 * win_stride + 2 * (size_t)(cap + 16);
+  if (cap > 64 * 1024) return arg_fail(ctx, MH_E_CAPACITY, "a FASTQ record exceeds 64 KiB");
+  P.size_rows(hslot);   // (hslot: the longest reads part + '\n' of the unit, from the measure pass)
+  size_t lds = ((sizeof(TplMeta) * EW_T + 15) / 16) * 16 + (size_t)EW_T * 2 * P.win_stride + 2 * (size_t)(cap + 16);
   CorruptCfg cc{0, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
   if (ctx->corrupt_on && es.crrec.cap < 16 * (size_t)m + 64) {   // corruption switched on after this unit's measure
     MH_TRY(sync_writers(ctx));
     MH_TRY(ensure(ctx, es.crrec, 16 * (size_t)m + 64));
   }
   if (ctx->corrupt_on) {
-    if (rlen > ctx->corrupt_max_bp) {
-      stage_end(ctx);
-      return arg_fail(ctx, MH_E_ARG, "read length exceeds the BQ model's max_bp");
-    }
+    if (rlen > ctx->corrupt_max_bp) return arg_fail(ctx, MH_E_ARG, "read length exceeds the BQ model's max_bp");
     cc = corrupt_cfg(ctx, unit_key, t_begin);
   }
-  if (lds > 160 * 1024) {
-    stage_end(ctx);
-    return arg_fail(ctx, MH_E_CAPACITY, "read length too large for the LDS staging layout");
-  }
+  if (lds > 160 * 1024) return arg_fail(ctx, MH_E_CAPACITY, "read length too large for the LDS staging layout");
   char *o1 = (char *)ctx->out1.p + ctx->used1;
   char *o2 = write_fastq2 ? (char *)ctx->out2.p + ctx->used2 : nullptr;
-  const int32_t head = (int32_t)(((q.prefix_len + q.mid_len + 10 + 16) + 15) / 16 * 16);
-  // qname buffer per template (emit_tile): head room, then the reads part (hslot: the longest reads part + '\n' of
-  // the unit, from the measure pass)
-  const int32_t qstride = head + (hslot > 16 ? (hslot + 15) / 16 * 16 : 16) + 32 + ED_QPAD;
-  const bool cr_rows = ctx->corrupt_on && cr_rows_lds(write_fastq2 ? 2 : 1, rlen, ctx->corrupt_n_bq);
-  const size_t lds_d = ed_lds_bytes(win_stride, qstride, rlen, write_fastq2 ? 2 : 1, cr_rows);
-  QHead qh{};
-  const bool head_fits = prefix.size() + mid.size() <= sizeof(qh.w);
-  if (head_fits) {
-    std::string pm = prefix + mid;
-    std::memcpy(qh.w, pm.data(), pm.size());
-    qh.lp = (int32_t)prefix.size();
-    qh.lm = (int32_t)mid.size();
-  }
-  if (direct && head_fits && win_stride <= 16 * 3 * ED_GMAX && lds_d <= 64 * 1024 &&
-      cnt_base + m < (int64_t)UINT32_MAX) {
-    if (cr_rows) MH_TRY(cr_rows_alloc(ctx, m, write_fastq2 ? 2 : 1, rlen));
-    // the direct writer, queued on the writer stream: the call returns while it runs, so the next unit's measure pass
-    // and the next job's sampling overlap it
-    if (!writer_dep) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_ready, st));
-      writer_dep = ctx->ev_ready;
-    }
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->wstream, writer_dep, 0));
-    ctx->stage_stream = ctx->wstream;
-    TArgs A{hv, m, pos0, pos1, fo0, recs, (const E3 *)es.tpre.p, {(char *)ctx->out1.p, (char *)ctx->out2.p},
-            {ctx->used1, ctx->used2}, cnt_base, (uint2 *)es.crrec.p, (int32_t)rlen, win_stride, head,
-            qstride};
-    if (cr_rows) MH_TRY(cr_rows_prepare(ctx, ctx->wstream, m, write_fastq2 ? 2 : 1, (int32_t)rlen, cc, A));
-    stage_begin(ctx, "emit_write");   // (after the row pass: the stage times the writer alone)
-    auto kfn = ew_kernel(cr_rows ? 2 : ctx->corrupt_on ? 1 : 0, write_fastq2);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)ntiles), dim3(ED_THREADS), lds_d, ctx->wstream, A, qh);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
-    hipStream_t tail = ctx->wstream;   // the stream whose last work is this unit's last
-    if (ctx->corrupt_on && !cr_rows)   // (tables too large for the row pass's LDS): in place after the writer
-      MH_TRY(launch_cr_inplace(ctx, tail, hv, m, pos0, pos1, fo0, recs, nullptr, (uint2 *)es.crrec.p,
-                               (char *)ctx->out1.p, (char *)ctx->out2.p, write_fastq2 ? 2 : 1,
-                               (int32_t)(prefix.size() + mid.size()), (int32_t)rlen, cc, true));
-    stage_end(ctx);   // "emit"
-    ctx->stage_stream = nullptr;
-    HIPCHK(ctx, hipEventRecord(es.done, tail));
-    HIPCHK(ctx, hipEventRecord(ctx->ev_writer, tail));
-    MH_TRY(mark_used(ctx, h.used, h.used_set));     // the haplotype and the templates stay live until then
-    MH_TRY(mark_used(ctx, tp.used, tp.used_set));
-    es.busy = true;
-    ctx->writer_pending = true;
+  if (direct && P.direct_ok && cnt_base + m < (int64_t)UINT32_MAX) {
+    if (P.cr == 2) MH_TRY(cr_rows_alloc(ctx, m, P.nf, rlen));
+    TArgs A = writer_args(ctx, P, hv, tp, t_begin, m, cnt_base, &es);
+    A.crec = (uint2 *)es.crrec.p;
+    MH_TRY(queue_writer(ctx, P, A, false, cc, writer_dep, &es, h, tp, emit));
   } else {
     // LDS-image writer: the fallback (very long qnames or names; synchronous, main stream); per-template offsets
     if (direct) {
@@ -2396,21 +2471,21 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
     HIPCHK(ctx, hipMemsetAsync(small + 32, 0, 16, st));
     HIPCHK(ctx, hipMemcpyAsync(d_prefix, prefix.data(), prefix.size(), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(d_mid, mid.data(), mid.size(), hipMemcpyHostToDevice, st));
-    stage_begin(ctx, "emit_write");
-    const int64_t nblk = (m + EW_T - 1) / EW_T;
-    hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk), dim3(EW_THREADS), lds, st, hv, m,
-                       pos0, pos1, fo0, rlen, q, recs, off, o1, o2, write_fastq2, cap, win_stride,
-                       (int32_t)ctx->corrupt_on, err);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
+    {
+      StageScope stage(ctx, "emit_write");
+      const int64_t nblk = (m + EW_T - 1) / EW_T;
+      hipLaunchKernelGGL(k_emit_write, dim3((unsigned)nblk), dim3(EW_THREADS), lds, st, hv, m,
+                         pos0, pos1, fo0, rlen, q, recs, off, o1, o2, write_fastq2, cap, P.win_stride,
+                         (int32_t)ctx->corrupt_on, err);
+      HIPCHK(ctx, hipGetLastError());
+    }
     if (ctx->corrupt_on)
-      MH_TRY(launch_cr_inplace(ctx, st, hv, m, pos0, pos1, fo0, recs, off, (uint2 *)es.crrec.p, o1, o2,
-                               write_fastq2 ? 2 : 1,
+      MH_TRY(launch_cr_inplace(ctx, st, hv, m, pos0, pos1, fo0, recs, off, (uint2 *)es.crrec.p, o1, o2, P.nf,
                                (int32_t)(prefix.size() + mid.size()), (int32_t)rlen, cc));
     int32_t herr = 0;
     HIPCHK(ctx, hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
     SYNCCHK(ctx, hipStreamSynchronize(st));
-    stage_end(ctx);
+    emit.end();
     if (herr) return arg_fail(ctx, MH_E_CAPACITY, "FASTQ record larger than the LDS staging image");
   }
   ctx->used1 += ht.b1;
@@ -2422,46 +2497,25 @@ int32_t emit_reads(mh_ctx *ctx, const Hap &h, int32_t slot, const char *serial_s
 }
 
 // ---- the single-pass writer's host side -----------------------------------------------------------------------
-using EfKernel = void (*)(TArgs, QHead);
-static EfKernel ef_kernel(int cr, bool two) {
-  return cr == 2 ? (two ? k_emit_fused<2, 4, 2, 3> : k_emit_fused<1, 8, 2, 3>)
-                 : (two ? k_emit_fused<2, 4, 0, 3> : k_emit_fused<1, 8, 0, 3>);
-}
-static int32_t ndig_host(int64_t v) {
-  int32_t d = 1;
-  for (; v >= 10; v /= 10) d++;
-  return d;
-}
-
 int32_t emit_unit_async(mh_ctx *ctx, const Hap &h, const char *serial_stub, const char *chrom, int64_t cpy,
                         int32_t write_fastq2, uint64_t unit_key, bool *queued) {
   *queued = false;
-  auto tit = ctx->tsets.find(ctx->cur_tpl);
-  if (tit == ctx->tsets.end() || !tit->second.valid)
-    return arg_fail(ctx, MH_E_STATE, "no templates: call mh_sample_templates / mh_use_templates first");
-  const TplSet &tp = tit->second;
+  const TplSet *tpp = nullptr;
+  MH_TRY(cur_templates(ctx, &tpp));
+  const TplSet &tp = *tpp;
   const int64_t m = tp.n, rlen = tp.rlen;
-  const int32_t nf = write_fastq2 ? 2 : 1;
-  const std::string prefix = std::string("@") + serial_stub + ":";
-  const std::string mid = std::string("|") + chrom + "|" + std::to_string(cpy);
   // what the single-pass writer covers (the rest takes emit_reads: the LDS-image writer, long names, reads past
   // the windows the splice bounded, the in-place corruption)
   if (ctx->emit_lds_only || ctx->emit_two_pass || !h.bound_valid || m >= (int64_t)UINT32_MAX) return MH_OK;
   int w = 0;
   while (w < PB_NW && PB_W[w] < rlen) w++;
-  QHead qh{};
-  if (w == PB_NW || prefix.size() + mid.size() > sizeof(qh.w)) return MH_OK;
-  const bool cr_rows = ctx->corrupt_on && cr_rows_lds(nf, rlen, ctx->corrupt_n_bq);
-  if (ctx->corrupt_on && (!cr_rows || rlen > ctx->corrupt_max_bp)) return MH_OK;
+  if (w == PB_NW) return MH_OK;
   // a read's qname part: '|' s '|' POS '|' rlen '|' + its nodes' CIGAR and v_list bytes (the splice's bound) + '|'
   const int32_t part_b = 3 + std::max(ndig_host(h.pos_max), 2) + 1 + ndig_host(rlen) + 1 + 1 + h.part_w[w];
   const int32_t hslot = 2 * part_b + 1;   // both reads' parts + '\n'
-  const int32_t win_stride = (int32_t)(((rlen + 31) / 16) * 16);
-  const int32_t head = (int32_t)(((prefix.size() + mid.size() + 10 + 16) + 15) / 16 * 16);
-  const int32_t hrow = (hslot + 15) / 16 * 16;
-  const int32_t qstride = head + hrow + 32 + ED_QPAD;
-  const size_t lds_d = ed_lds_bytes(win_stride, qstride, rlen, nf, cr_rows);
-  if (win_stride > 16 * 3 * ED_GMAX || lds_d > 64 * 1024) return MH_OK;
+  const WriterPlan P = writer_plan(ctx, rlen, serial_stub, chrom, cpy, write_fastq2, hslot);
+  if (!P.direct_ok || P.cr == 1 || (P.cr && rlen > ctx->corrupt_max_bp)) return MH_OK;
+  const size_t name_b = P.prefix.size() + P.mid.size();
   // the default: the measure pass and the tile scan queued on the main stream, the writer on the writer stream, the
   // unit's offsets and totals passed on the device (no readback); mh_set_emit_mode(3): the single-pass writer
   const bool single = ctx->emit_single;
@@ -2488,7 +2542,7 @@ int32_t emit_unit_async(mh_ctx *ctx, const Hap &h, const char *serial_stub, cons
     ctx->used_ub1 = ctx->used1;
     ctx->used_ub2 = ctx->used2;
   }
-  const int64_t rec_b = (int64_t)(prefix.size() + mid.size()) + ndig_host(m) + hslot + 2 * rlen + 5;
+  const int64_t rec_b = (int64_t)name_b + ndig_host(m) + hslot + 2 * rlen + 5;
   const int64_t add = m * rec_b;
   // a growth reserves for the rest of the sampled batch too (its units' draws bound their templates), by an eighth
   // more, not by half: one reallocation per batch size instead of one every few units, and no superseded arenas
@@ -2501,52 +2555,27 @@ int32_t emit_unit_async(mh_ctx *ctx, const Hap &h, const char *serial_stub, cons
     MH_TRY(ensure_keep(ctx, ctx->out2, ctx->used_ub2 + add + rest + 64, ctx->used_ub2, 3));
   const int64_t ntiles = (m + ED_T - 1) / ED_T;
   const size_t lb_need = 64 + 48 * (size_t)ntiles + 64;
-  int32_t set = -1;
+  EmitSet *es = nullptr;
   if (single) {
     MH_TRY(ensure(ctx, ctx->fused_lb, lb_need));
   } else {
-    set = ctx->eset_i;
-    EmitSet &es = ctx->eset[set];
-    ctx->eset_i = (ctx->eset_i + 1) % mh_ctx::N_ESET;
-    if (m > ctx->eset_max_m) ctx->eset_max_m = m;
-    const int64_t mm = ctx->eset_max_m, mt = (mm + ED_T - 1) / ED_T;
-    MH_TRY(ensure(ctx, es.recs, sizeof(Rec) * mm));
-    MH_TRY(ensure(ctx, es.tsum, sizeof(int4) * (size_t)mt));
-    MH_TRY(ensure(ctx, es.tpre, sizeof(E3) * (size_t)mt));
-    MH_TRY(ensure(ctx, es.stat, 64));
-    MH_TRY(ensure(ctx, ctx->scan_partials, scan_lb_scratch_bytes<E3>(ntiles)));
+    int32_t set = -1;
+    MH_TRY(eset_reserve(ctx, m, ntiles, &set));
+    es = &ctx->eset[set];
   }
   CorruptCfg cc{0, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-  if (cr_rows) {
+  if (P.cr == 2) {
     cc = corrupt_cfg(ctx, unit_key, 0);
-    MH_TRY(cr_rows_alloc(ctx, m, nf, rlen));
+    MH_TRY(cr_rows_alloc(ctx, m, P.nf, rlen));
   }
   // (every allocation above may drain the writers; from here on nothing does)
-  const std::string pm = prefix + mid;
-  std::memcpy(qh.w, pm.data(), pm.size());
-  qh.lp = (int32_t)prefix.size();
-  qh.lm = (int32_t)mid.size();
   const int64_t seq = ctx->lazy_seq;
   const int32_t rslot = (int32_t)(seq % mh_ctx::LZ_SLOTS);
   int64_t *d_cur = (int64_t *)ctx->d_cur.p;
   hipStream_t ws = ctx->wstream;
   uint32_t tbase = 0, epoch = 0;
   if (single) HIPCHK(ctx, lb_reserve(ws, ctx->fused_lb.p, lb_need, (uint32_t)ntiles, &tbase, &epoch));
-  TArgs A{};
-  A.h = view_of(h);
-  A.m = m;
-  A.pos0 = (const int64_t *)tp.pos0.p;
-  A.pos1 = (const int64_t *)tp.pos1.p;
-  A.fo0 = (const int8_t *)tp.fo0.p;
-  A.arena[0] = (char *)ctx->out1.p;
-  A.arena[1] = (char *)ctx->out2.p;
-  A.used[0] = ctx->used1;
-  A.used[1] = ctx->used2;
-  A.cnt_base = 0;
-  A.rlen = (int32_t)rlen;
-  A.win_stride = win_stride;
-  A.head = head;
-  A.qstride = qstride;
+  TArgs A = writer_args(ctx, P, view_of(h), tp, 0, m, 0, es);
   A.nb = 1;
   A.lb = single ? (uint64_t *)ctx->fused_lb.p : nullptr;
   A.ntiles = ntiles;
@@ -2558,48 +2587,13 @@ int32_t emit_unit_async(mh_ctx *ctx, const Hap &h, const char *serial_stub, cons
   A.res = ctx->d_lazy + 8 * rslot;
   A.cap[0] = (int64_t)ctx->out1.cap;
   A.cap[1] = write_fastq2 ? (int64_t)ctx->out2.cap : 0;
-  A.hcap = hrow;
+  A.hcap = P.hrow;
   // the writer waits for what the main stream has queued (this unit's templates: its sampling tail was joined there
   // by tpl_resolve; its measure pass and tile scan), not for any host readback
-  stage_begin(ctx, "emit");
-  if (!single) {
-    EmitSet &es = ctx->eset[set];
-    hipStream_t st = ctx->stream;
-    if (es.busy) HIPCHK(ctx, hipStreamWaitEvent(st, es.done, 0));   // the writer that last read the set
-    char *stat = (char *)es.stat.p;   // (its maxima are not read: the splice's bound sizes the rows)
-    stage_begin(ctx, "emit_measure");
-    hipLaunchKernelGGL(k_emit_measure, dim3(grid_for(m, 256, INT32_MAX)), dim3(256), 0, st, A.h, m, A.pos0, A.pos1,
-                       A.fo0, rlen, QFixed{nullptr, nullptr, qh.lp, qh.lm}, (int32_t)ctx->corrupt_on,
-                       (Rec *)es.recs.p, (int4 *)es.tsum.p, (int32_t *)(stat + 32),
-                       tp.has_n0 ? (const int32_t *)tp.n0.p : nullptr);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
-    stage_begin(ctx, "emit_scan");
-    HIPCHK(ctx, device_scan_sum<E3>(st, ntiles, LoadTile{(const int4 *)es.tsum.p, ntiles},
-                                    StoreTile{(E3 *)es.tpre.p}, ctx->scan_partials.p, (E3 *)stat));
-    stage_end(ctx);
-    A.recs = (const Rec *)es.recs.p;
-    A.tpre = (const E3 *)es.tpre.p;
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->ev_ready, ctx->stream));
-  HIPCHK(ctx, hipStreamWaitEvent(ws, ctx->ev_ready, 0));
-  ctx->stage_stream = ws;
-  if (cr_rows) MH_TRY(cr_rows_prepare(ctx, ws, m, nf, (int32_t)rlen, cc, A));
-  stage_begin(ctx, "emit_write");
-  hipLaunchKernelGGL(single ? ef_kernel(cr_rows ? 2 : 0, write_fastq2 != 0) : ew_kernel(cr_rows ? 2 : 0, write_fastq2),
-                     dim3((unsigned)ntiles), dim3(ED_THREADS), lds_d, ws, A, qh);
-  HIPCHK(ctx, hipGetLastError());
-  stage_end(ctx);
-  stage_end(ctx);   // "emit"
-  ctx->stage_stream = nullptr;
-  if (!single) {
-    HIPCHK(ctx, hipEventRecord(ctx->eset[set].done, ws));
-    ctx->eset[set].busy = true;
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->ev_writer, ws));
-  MH_TRY(mark_used(ctx, h.used, h.used_set));     // the haplotype and the templates stay live until then
-  MH_TRY(mark_used(ctx, tp.used, tp.used_set));
-  ctx->writer_pending = true;
+  StageScope emit(ctx, "emit");
+  if (es)   // (the set's maxima are not read, nor zeroed: the splice's bound sizes the rows)
+    MH_TRY(queue_measure(ctx, *es, A.h, tp, 0, m, QFixed{nullptr, nullptr, P.qh.lp, P.qh.lm}, true));
+  MH_TRY(queue_writer(ctx, P, A, single, cc, nullptr, es, h, tp, emit));
   ctx->chain_open = true;
   ctx->used_ub1 += add;
   if (write_fastq2) ctx->used_ub2 += add;

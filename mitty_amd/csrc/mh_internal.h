@@ -451,6 +451,34 @@ int32_t prefetch_words(mh_ctx *ctx, hipStream_t st, int32_t n_units, const int64
 void stage_begin(mh_ctx *ctx, const char *name);
 void stage_end(mh_ctx *ctx);
 void stages_collect(mh_ctx *ctx);
+// A stage open for a scope: every way out of the scope ends it (end(): before the scope does).
+struct StageScope {
+  mh_ctx *ctx;
+  bool open = true;
+  StageScope(mh_ctx *c, const char *name) : ctx(c) { stage_begin(c, name); }
+  StageScope(const StageScope &) = delete;
+  StageScope &operator=(const StageScope &) = delete;
+  void end() {
+    if (open) stage_end(ctx);
+    open = false;
+  }
+  ~StageScope() { end(); }
+};
+// The stage timing events on stream `st` for a scope (ctx->stage_stream, restored on the way out).
+struct StageStreamScope {
+  mh_ctx *ctx;
+  hipStream_t prev;
+  StageStreamScope(mh_ctx *c, hipStream_t st) : ctx(c), prev(c->stage_stream) { c->stage_stream = st; }
+  StageStreamScope(const StageStreamScope &) = delete;
+  StageStreamScope &operator=(const StageStreamScope &) = delete;
+  ~StageStreamScope() { ctx->stage_stream = prev; }
+};
+
+// A template set's preparation (mh_emit_prepare) dropped: its buffer set is free again.
+inline void prep_drop(mh_ctx *ctx, const TplSet &tp) {
+  if (tp.prep.valid) ctx->eset[tp.prep.set].prepared = false;
+  tp.prep.valid = false;
+}
 
 // Launch helpers
 inline unsigned grid_for(int64_t n, int threads, int64_t cap = 1 << 20) {

@@ -623,6 +623,64 @@ def test_prefetched_haplotypes_vs_build(native):
     assert a[i][1][0] == a[len(batches) + i][1][0]   # (the second step repeats the first)
 
 
+@pytest.fixture(scope='module')
+def inflight(native):
+  """A bare context with slot 0 built from a 300 kbp contig's resident variants, one template set sampled on it, and
+  that unit's FASTQ and totals through mh_emit_reads: what an emission on any slot spliced from the same contig and
+  variants writes (its nodes, and the start nodes the templates carry, are slot 0's)."""
+  from mitty_amd import synth
+  mdl = G.model('hiseq-X-v2.5-Garvan')
+  p, _ = native.read_model_params(150, 30.0)
+  seq = synth.contig(300_000, 71)
+  c = native.Context(0)
+  try:
+    c.upload_contig(0, seq)
+    c.upload_variants(0, synth.copies_soa(synth.variants(seq, 72))[0])
+    c.build_haplotype_vset(0, 0, 1, 0)
+    assert c.sample_templates(0, p, 150, mdl['cum_tlen'], 73) > 0
+    totals = c.emit_reads(0, 'PJ:0:0', '9', 0)
+    f1, f2 = c.fetch_output()
+    assert totals[0] > 0 and (len(f1), len(f2)) == totals[1:]
+    yield c, totals, np.frombuffer(f1, np.uint8), np.frombuffer(f2, np.uint8)
+  finally:
+    c.close()
+
+
+@pytest.mark.parametrize('entry', ['reads', 'range', 'prepare', 'async', 'measure'])
+def test_emission_joins_an_inflight_prefetch(inflight, entry):
+  """Every emission entry point called right after mh_prefetch_haplotypes_vset, on the slot the prefetch thread is
+  still splicing: the call joins the prefetch instead of finding the slot empty (MH_E_STATE), and writes what the
+  same unit writes from slot 0.  mh_emit_measure returns the same totals and writes nothing."""
+  c, totals, want1, want2 = inflight
+  args = (1, 'PJ:0:0', '9', 0)
+  c.reset_output()
+  c.prefetch_haplotypes_vset([1], [0], [1], [0])
+  try:
+    if entry == 'reads':
+      got = c.emit_reads(*args)
+    elif entry == 'range':
+      got = c.emit_reads(*args, t_range=(0, 1 << 40))
+    elif entry == 'prepare':
+      c.emit_prepare(*args)
+      got = c.emit_reads(*args)
+    elif entry == 'async':
+      c.emit_async(*args)
+      got, = c.emit_collect()
+    else:
+      got = c.emit_measure(*args)
+    assert got == totals
+    if entry == 'measure':
+      assert c.output_size() == (0, 0)
+    else:
+      assert c.output_size() == totals[1:]
+      got1, got2 = c.fetch_output_arrays(0, totals[1], 0, totals[2])
+      assert np.array_equal(got1, want1)
+      assert np.array_equal(got2, want2)
+  finally:
+    c.count_kept(0, 0, 0)    # (joins the prefetch thread whatever happened above)
+    c.release_haplotype(1)   # (a prefetch takes a free slot)
+
+
 def test_lsd_sort_repeated_batches(native):
   """The permutation sort (mh_sort.h) over batches of different sizes and then the first batch again: its look-back
   status words sit inside the sort's buffer at an offset that moves with the batch size, so a batch size seen before
