@@ -24,6 +24,7 @@
  *   mh_read_model_params  illumina.read_model_params                     mitty/simulation/illumina.py:12-40
  *   mh_bamfile_next       pysam.AlignmentFile.fetch                      mitty/benchmarking/mq.py:61-62
  *   mh_score_add_records  mq / derr process_bam_part                     mitty/benchmarking/mq.py:50-68, derr.py:53-76
+ *   mh_model_add_records  bam2illumina.process_bam_section               mitty/empirical/bam2illumina.py:17-59, 84-105
  *
  * Threading: one mh_ctx per GPU and per host thread; a context owns one HIP stream and all device buffers.
  * Calls are synchronous at return (device work is ordered on the context's stream; results copied back are
@@ -407,6 +408,32 @@ int32_t mh_score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, cons
 int32_t mh_score_add_store(mh_ctx *ctx);
 int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
 int32_t mh_score_reset(mh_ctx *ctx);
+
+/* ---- read model from a BAM: bam2illumina (process_bam_section, mitty/empirical/bam2illumina.py:17-59, summed over
+ * the header's first 24 @SQ by process_bam_parallel, :84-105; cli.py:54-68).  One pass over BAM records on the device:
+ *   bq_mat    u64[2][max_bp][max_bq]   bq_mat[0 if flag & 0x40 else 1, i, Q_i] += 1, Q reversed for flag & 0x10
+ *   tlen_mat  u64[max_tlen]            tlen_mat[|tlen|] += 1 for read2 records with min_mq <= MAPQ != 255, |tlen| < max_tlen
+ * A record with tid < 0 is not visited; one with 24 <= tid < n_refs is skipped; of the records of one tid, in the
+ * order given and whatever their flags, only every `every`-th is looked at (the first is), and of those the ones with
+ * flag > 255 are skipped.  A visited record with tid >= n_refs, a used record with l_seq 0, l_seq > max_bp or a
+ * quality >= max_bq (0xff fill included) is MH_E_ARG naming the first such record (the reference raises); once a record
+ * fails nothing of its call or of a later one is kept.  All sums are exact and independent of the chunking.
+ *   mh_model_begin        a new session; every >= 1, 1 <= max_bq <= 256, max_bp, max_tlen >= 1, 2 max_bp max_bq < 2^31
+ *   mh_model_add_records  as mh_score_add_records: checked on the host, staged in one of two page-locked buffers, queued
+ *   mh_model_add_store    the context's own BAM record store in HBM, in the store's order (input order, or coordinate
+ *                         order after a direct sorted write); n_refs is the store's (mh_bam_set_refs); a spilled store
+ *                         is refused
+ *   mh_model_result       waits; the matrices (either may be NULL) and counts[8] = records seen, used, skipped for
+ *                         tid < 0, for tid >= 24, by `every`, by flag > 255, min l_seq, max l_seq of the used records
+ *                         (MH_MODEL_NO_RLEN and 0 when none was used)
+ *   mh_model_reset        zero sums, ordinals from 0 and no error, same session parameters */
+#define MH_MODEL_NO_RLEN INT64_MAX
+int32_t mh_model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
+                       int32_t max_tlen);
+int32_t mh_model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t mh_model_add_store(mh_ctx *ctx);
+int32_t mh_model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts);
+int32_t mh_model_reset(mh_ctx *ctx);
 
 /* ---- VCF ingest (vcfio.load_variant_file / split_copies / parse, vcfio.py:51-126) ------
  * Host-only (no device): mh_vcf_open parses a plain or bgzipped VCF for one sample; mh_vcf_region runs the BED

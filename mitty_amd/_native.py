@@ -30,7 +30,11 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_vcf_open', 'mh_vcf_error', 'mh_vcf_close', 'mh_vcf_region', 'mh_vcf_copy', 'mh_vcf_filter',
            'mh_bamfile_open', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
            'mh_score_begin', 'mh_score_add_records', 'mh_score_add_store', 'mh_score_result', 'mh_score_reset',
+           'mh_model_begin', 'mh_model_add_records', 'mh_model_add_store', 'mh_model_result', 'mh_model_reset',
            'mh_fasta_open', 'mh_fasta_error', 'mh_fasta_count', 'mh_fasta_contig', 'mh_fasta_copy', 'mh_fasta_close']
+
+
+MODEL_NO_RLEN = (1 << 63) - 1   # MH_MODEL_NO_RLEN: counts[6] of mh_model_result when no record was used
 
 
 class NativeError(RuntimeError):
@@ -155,6 +159,11 @@ def lib():
   _sig(L, 'mh_score_add_store', [c_vp])
   _sig(L, 'mh_score_result', [c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_score_reset', [c_vp])
+  _sig(L, 'mh_model_begin', [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32])
+  _sig(L, 'mh_model_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
+  _sig(L, 'mh_model_add_store', [c_vp])
+  _sig(L, 'mh_model_result', [c_vp, c_vp, c_vp, c_vp])
+  _sig(L, 'mh_model_reset', [c_vp])
   _sig(L, 'mh_fasta_open', [ctypes.c_char_p, c_vp, ctypes.POINTER(c_vp)])
   _sig(L, 'mh_fasta_error', [c_vp], ctypes.c_char_p)
   _sig(L, 'mh_fasta_count', [c_vp, ctypes.POINTER(c_i32)])
@@ -984,6 +993,44 @@ class Context:
 
   def score_reset(self):
     self._chk(self._L.mh_score_reset(self._h))
+
+  # ---- read model from a BAM (bam2illumina) ----
+  def model_begin(self, n_refs, every=1, min_mq=0, max_bq=94, max_bp=300, max_tlen=1000):
+    """A new read-model session over a BAM whose header lists n_refs references (the first 24 are visited)."""
+    self._chk(self._L.mh_model_begin(self._h, int(n_refs), int(every), int(min_mq), int(max_bq), int(max_bp),
+                                     int(max_tlen)))
+    self._model_shape = (int(max_bp), int(max_bq), int(max_tlen))
+
+  def model_add_raw(self, recs_addr, nbytes, roff_addr, n):
+    """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by model_result."""
+    self._chk(self._L.mh_model_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+
+  def model_add_records(self, recs, roff):
+    """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
+    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
+    o = np.ascontiguousarray(roff, dtype=np.int64)
+    self._chk(self._L.mh_model_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+
+  def model_add_store(self):
+    """The context's own BAM record store (bam_add_fastq / bam_add_output) through the session, in HBM."""
+    self._chk(self._L.mh_model_add_store(self._h))
+
+  def model_result(self):
+    """(bq_mat u64[2, max_bp, max_bq], tlen u64[max_tlen], counts dict).  min_rlen is None when no record was used
+    (max_rlen is then 0)."""
+    max_bp, max_bq, max_tlen = self._model_shape
+    bq = np.zeros((2, max_bp, max_bq), np.uint64)
+    tl = np.zeros(max_tlen, np.uint64)
+    cnt = np.zeros(8, np.int64)
+    self._chk(self._L.mh_model_result(self._h, _ptr(bq), _ptr(tl), _ptr(cnt)))
+    d = dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_every', 'skipped_flag', 'min_rlen',
+                  'max_rlen'), (int(x) for x in cnt)))
+    if d['min_rlen'] == MODEL_NO_RLEN:
+      d['min_rlen'] = None
+    return bq, tl, d
+
+  def model_reset(self):
+    self._chk(self._L.mh_model_reset(self._h))
 
   def bam_partition(self, splitters, tie_base):
     """The store's records by destination rank (mh_bam_partition): returns (segment offsets [n_dest + 1], records

@@ -1,11 +1,12 @@
 """`mitty` command line (reference mitty/cli.py), MI355X build.
 
 Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), mq-plot and derr-plot (GPU scoring, host
-BAM reader; additive --device), filter-variants (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
+BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; additive --device), filter-variants
+(host C++), qname, list-read-models.  Additive options on generate-reads: --device,
 --rng {mitty,philox}, --corrupt-seed (fused Philox corruption); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
 RCCL); the output files are identical to the one-GPU run.  Out of scope for this build (not on the
-generate-reads path): filter-bam, gc-cov, bq, bam2illumina, describe-read-model.
+generate-reads path): filter-bam, gc-cov, bq, describe-read-model.
 """
 import logging
 import os
@@ -31,6 +32,25 @@ def filter_vcf(vcfin, sample, bed, vcfout):
    making it suitable to use for read generation (reference cli.py:20-35)"""
   from mitty_amd.lib import vcfio
   vcfio.prepare_variant_file(vcfin, sample, bed, vcfout)
+
+
+@cli.command('bam2illumina', short_help='Create read model from BAM file')
+@click.argument('bam', type=click.Path(exists=True))
+@click.argument('pkl')
+@click.argument('desc')
+@click.option('--every', type=int, default=1, help='Sample every nth read')
+@click.option('--min-mq', type=int, default=0, help='Discard reads with MQ less than this')
+@click.option('-t', '--threads', type=int, default=2, help='Threads to use')
+@click.option('--max-bp', type=int, default=300, help='Maximum length of read')
+@click.option('--max-tlen', type=int, default=1000, help='Maximum size of insert')
+@click.option('--device', default=0, help='HIP device ordinal')
+def bam2illumina(bam, pkl, desc, every, min_mq, threads, max_bp, max_tlen, device):
+  """Process BAM file and create an empirical model of template length and base quality
+  distribution. The model is saved to a Python pickle file usable by Mitty read generation programs
+  (reference cli.py:54-68)."""
+  from mitty_amd.empirical import bam2illumina as b2m
+  b2m.process_bam_parallel(bam, pkl, model_description=desc, every=max(1, every), min_mq=min_mq,
+                           threads=threads, max_bq=94, max_bp=max_bp, max_tlen=max_tlen, device=device)
 
 
 @cli.command('list-read-models')

@@ -545,6 +545,7 @@ int32_t mh_destroy(mh_ctx *ctx) {
   (void)hipStreamDestroy(ctx->wstream);
   bam_release(ctx->bam);
   score_release(ctx->score);
+  model_release(ctx->model);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1844,6 +1845,34 @@ int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64
 int32_t mh_score_reset(mh_ctx *ctx) {
   CTX_GUARD(ctx);
   return score_reset(ctx);
+}
+
+// ---- read model from a BAM: bam2illumina (mh_model.hip) ---------------------------------------------------------
+int32_t mh_model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
+                       int32_t max_tlen) {
+  CTX_GUARD(ctx);
+  return model_begin(ctx, n_refs, every, min_mq, max_bq, max_bp, max_tlen);
+}
+
+int32_t mh_model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  CTX_GUARD(ctx);
+  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  return model_add_records(ctx, recs, len, roff, n);
+}
+
+int32_t mh_model_add_store(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return model_add_store(ctx);
+}
+
+int32_t mh_model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts) {
+  CTX_GUARD(ctx);
+  return model_result(ctx, bq_mat, tlen_mat, counts);
+}
+
+int32_t mh_model_reset(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return model_reset(ctx);
 }
 
 }  // extern "C"

@@ -219,6 +219,23 @@ struct BamStore {
   std::string spill_dir;       // mh_bam_set_spill_dir: spill to files there (the page cache, not anonymous memory)
 };
 
+// Host BAM records on their way to the device, shared by the sessions that take records from the host reader
+// (mh_score.hip, mh_model.hip): two page-locked buffers, so chunk k + 1 is checked and copied while chunk k is worked on.
+struct RecStage {
+  DevBuf in[2];                // the chunk on the device: record offsets, then the records
+  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked staging, one per chunk in flight
+  size_t pin_cap[2] = {0, 0};
+  hipEvent_t ev[2] = {nullptr, nullptr};  // after the kernels of the chunk staged in pin[k]
+  bool ev_set[2] = {false, false};
+  int cur = 0;
+};
+struct StagedRecs {
+  const uint8_t *recs;         // device: the records, 64 zero bytes behind them
+  const int64_t *roff;         // device: n + 1 offsets from recs
+  int64_t avail;               // bytes readable at recs
+  int slot;
+};
+
 // Alignment scorer (mh_score.hip): both matrices and the counts of one scoring session, resident until read back.
 struct ScoreState {
   bool begun = false;
@@ -227,13 +244,24 @@ struct ScoreState {
   DevBuf acc, delta;           // [mq_mat | d_err_mat | counts]: the session's sums / the chunk being scored
   DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
   DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
-  DevBuf in[2];                // the chunk on the device: record offsets, then the records
-  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked staging, one per chunk in flight
-  size_t pin_cap[2] = {0, 0};
-  hipEvent_t ev[2] = {nullptr, nullptr};  // after the kernels of the chunk staged in pin[k]
-  bool ev_set[2] = {false, false};
-  int cur = 0;
+  RecStage stage;
   int64_t base_rec = 0;        // records given to earlier calls (names a failing record)
+};
+
+// Read-model builder (mh_model.hip, bam2illumina): the session's histograms, resident until read back.
+struct ModelState {
+  static constexpr int N_REF = 24;   // refs[:24]: only the header's first 24 @SQ are visited
+  bool begun = false;
+  int32_t n_refs = 0, every = 1, min_mq = 0, max_bq = 0, max_bp = 0, max_tlen = 0;
+  int32_t slab_bp = 0, n_slab = 0;   // base positions per LDS table, tables per mate
+  int64_t n_bq = 0, n_all = 0;       // u64 cells of bq_mat; of everything
+  // [bq_mat | tlen | 6 counts, INT32_MAX - min_rlen, max_rlen | records per refID (N_REF)]: the session's / the chunk's
+  DevBuf acc, delta;
+  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
+  DevBuf desc;                 // per record of the chunk: where its qualities are, l_seq, mate and strand
+  DevBuf tile_ord;             // every > 1: per 256-record tile and refID the ordinal of the tile's first such record
+  RecStage stage;
+  int64_t base_rec = 0;
 };
 
 struct StageTime {
@@ -406,6 +434,8 @@ struct mh_ctx {
   mh::BamStore bam;
   // mq-plot / derr-plot scoring session
   mh::ScoreState score;
+  // bam2illumina session
+  mh::ModelState model;
 };
 
 namespace mh {
@@ -575,6 +605,22 @@ int32_t score_add_store(mh_ctx *ctx);
 int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
 int32_t score_reset(mh_ctx *ctx);
 void score_release(ScoreState &S);
+// the staging half of a session's add_records (mh_score.hip): the n records checked as the reader checks them
+// (bam_record_ok; a failure names record base_rec + i), copied with their offsets into the free page-locked buffer and
+// queued for upload; the caller queues its kernels on ctx->stream, then calls stage_queued(out->slot)
+int32_t stage_records(mh_ctx *ctx, RecStage &G, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n,
+                      int64_t base_rec, StagedRecs *out);
+int32_t stage_queued(mh_ctx *ctx, RecStage &G, int slot);
+int32_t stage_init(mh_ctx *ctx, RecStage &G);   // its events exist; the chunks in flight are done
+void stage_release(RecStage &G);
+// read-model histograms (mh_model.hip)
+int32_t model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
+                    int32_t max_tlen);
+int32_t model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t model_add_store(mh_ctx *ctx);
+int32_t model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts);
+int32_t model_reset(mh_ctx *ctx);
+void model_release(ModelState &S);
 int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_t *d1, int64_t len1, int64_t t_base,
                       int64_t *used0, int64_t *used1, int64_t *templates);
 

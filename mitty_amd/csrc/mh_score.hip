@@ -334,11 +334,7 @@ int32_t score_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int6
 
 int32_t score_clear(mh_ctx *ctx) {
   ScoreState &S = ctx->score;
-  for (int k = 0; k < 2; k++)
-    if (S.ev_set[k]) {
-      HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
-      S.ev_set[k] = false;
-    }
+  MH_TRY(stage_init(ctx, S.stage));
   HIPCHK(ctx, hipMemsetAsync(S.acc.p, 0, sizeof(uint64_t) * S.n_all, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, ctx->stream));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -377,11 +373,7 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   S.n_refs = n_refs;
   S.plen = (int32_t)pre.size();
   hipStream_t st = ctx->stream;
-  for (int k = 0; k < 2; k++)
-    if (S.ev_set[k]) {
-      HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
-      S.ev_set[k] = false;
-    }
+  MH_TRY(stage_init(ctx, S.stage));
   MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.err, 64));
@@ -391,52 +383,85 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   if (!cat.empty()) HIPCHK(ctx, hipMemcpyAsync(S.names.p, cat.data(), cat.size(), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(S.name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
   if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(S.prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
-  for (int k = 0; k < 2; k++)
-    if (!S.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&S.ev[k], hipEventDisableTiming));
   MH_TRY(score_clear(ctx));   // (synchronises: the host strings above are done with)
   S.begun = true;
   return MH_OK;
+}
+
+int32_t stage_init(mh_ctx *ctx, RecStage &G) {
+  for (int k = 0; k < 2; k++) {
+    if (!G.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&G.ev[k], hipEventDisableTiming));
+    if (G.ev_set[k]) {
+      HIPCHK(ctx, hipEventSynchronize(G.ev[k]));
+      G.ev_set[k] = false;
+    }
+  }
+  return MH_OK;
+}
+
+int32_t stage_records(mh_ctx *ctx, RecStage &G, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n,
+                      int64_t base_rec, StagedRecs *out) {
+  // the same structural check the reader applies: nothing malformed reaches the device
+  if (roff[0] < 0 || roff[n] > len) return arg_fail(ctx, MH_E_ARG, "record offsets outside the buffer");
+  for (int64_t i = 0; i < n; i++) {
+    std::string why;
+    if (roff[i + 1] < roff[i] || roff[i + 1] > len || !bam_record_ok(recs + roff[i], roff[i + 1] - roff[i], &why))
+      return arg_fail(ctx, MH_E_ARG, "malformed BAM record " + std::to_string(base_rec + i) + ": " +
+                                         (why.empty() ? "record offsets decrease" : why));
+  }
+  const int k = G.cur;
+  if (G.ev_set[k]) {   // the chunk staged here two calls ago has been worked through
+    HIPCHK(ctx, hipEventSynchronize(G.ev[k]));
+    G.ev_set[k] = false;
+  }
+  const int64_t bytes = roff[n] - roff[0];
+  const size_t o_recs = ((size_t)(n + 1) * 8 + 15) & ~(size_t)15, need = o_recs + (size_t)bytes + 64;
+  if (G.pin_cap[k] < need) {
+    if (G.pin[k]) (void)hipHostFree(G.pin[k]);
+    G.pin[k] = nullptr;
+    G.pin_cap[k] = 0;
+    const size_t cap = need + need / 4;
+    HIPCHK(ctx, hipHostMalloc((void **)&G.pin[k], cap, hipHostMallocDefault));
+    G.pin_cap[k] = cap;
+  }
+  int64_t *po = (int64_t *)G.pin[k];
+  for (int64_t i = 0; i <= n; i++) po[i] = roff[i] - roff[0];
+  memcpy(G.pin[k] + o_recs, recs + roff[0], (size_t)bytes);
+  memset(G.pin[k] + o_recs + bytes, 0, 64);
+  MH_TRY(ensure(ctx, G.in[k], need));
+  HIPCHK(ctx, hipMemcpyAsync(G.in[k].p, G.pin[k], need, hipMemcpyHostToDevice, ctx->stream));
+  *out = StagedRecs{(const uint8_t *)G.in[k].p + o_recs, (const int64_t *)G.in[k].p, bytes + 64, k};
+  return MH_OK;
+}
+
+int32_t stage_queued(mh_ctx *ctx, RecStage &G, int slot) {
+  HIPCHK(ctx, hipEventRecord(G.ev[slot], ctx->stream));
+  G.ev_set[slot] = true;
+  G.cur = slot ^ 1;
+  return MH_OK;
+}
+
+void stage_release(RecStage &G) {
+  for (int k = 0; k < 2; k++) {
+    release(G.in[k]);
+    if (G.pin[k]) (void)hipHostFree(G.pin[k]);
+    if (G.ev[k]) (void)hipEventDestroy(G.ev[k]);
+    G.pin[k] = nullptr;
+    G.pin_cap[k] = 0;
+    G.ev[k] = nullptr;
+    G.ev_set[k] = false;
+  }
 }
 
 int32_t score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   ScoreState &S = ctx->score;
   if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
   if (n == 0) return MH_OK;
-  // the same structural check the reader applies: nothing malformed reaches the device
-  if (roff[0] < 0 || roff[n] > len) return arg_fail(ctx, MH_E_ARG, "record offsets outside the buffer");
-  for (int64_t i = 0; i < n; i++) {
-    std::string why;
-    if (roff[i + 1] < roff[i] || roff[i + 1] > len || !bam_record_ok(recs + roff[i], roff[i + 1] - roff[i], &why))
-      return arg_fail(ctx, MH_E_ARG, "malformed BAM record " + std::to_string(S.base_rec + i) + ": " +
-                                         (why.empty() ? "record offsets decrease" : why));
-  }
-  const int k = S.cur;
-  if (S.ev_set[k]) {   // the chunk staged here two calls ago has been scored
-    HIPCHK(ctx, hipEventSynchronize(S.ev[k]));
-    S.ev_set[k] = false;
-  }
-  const int64_t bytes = roff[n] - roff[0];
-  const size_t o_recs = ((size_t)(n + 1) * 8 + 15) & ~(size_t)15, need = o_recs + (size_t)bytes + 64;
-  if (S.pin_cap[k] < need) {
-    if (S.pin[k]) (void)hipHostFree(S.pin[k]);
-    S.pin[k] = nullptr;
-    S.pin_cap[k] = 0;
-    const size_t cap = need + need / 4;
-    HIPCHK(ctx, hipHostMalloc((void **)&S.pin[k], cap, hipHostMallocDefault));
-    S.pin_cap[k] = cap;
-  }
-  int64_t *po = (int64_t *)S.pin[k];
-  for (int64_t i = 0; i <= n; i++) po[i] = roff[i] - roff[0];
-  memcpy(S.pin[k] + o_recs, recs + roff[0], (size_t)bytes);
-  memset(S.pin[k] + o_recs + bytes, 0, 64);
-  MH_TRY(ensure(ctx, S.in[k], need));
-  HIPCHK(ctx, hipMemcpyAsync(S.in[k].p, S.pin[k], need, hipMemcpyHostToDevice, ctx->stream));
-  MH_TRY(score_launch(ctx, (const uint8_t *)S.in[k].p + o_recs, (const int64_t *)S.in[k].p, n, bytes + 64,
-                      (const char *)S.names.p, (const int32_t *)S.name_off.p, S.n_refs));
-  HIPCHK(ctx, hipEventRecord(S.ev[k], ctx->stream));
-  S.ev_set[k] = true;
-  S.cur ^= 1;
-  return MH_OK;
+  StagedRecs d;
+  MH_TRY(stage_records(ctx, S.stage, recs, len, roff, n, S.base_rec, &d));
+  MH_TRY(score_launch(ctx, d.recs, d.roff, n, d.avail, (const char *)S.names.p, (const int32_t *)S.name_off.p,
+                      S.n_refs));
+  return stage_queued(ctx, S.stage, d.slot);
 }
 
 int32_t score_add_store(mh_ctx *ctx) {
@@ -486,13 +511,7 @@ int32_t score_reset(mh_ctx *ctx) {
 
 void score_release(ScoreState &S) {
   release(S.acc); release(S.delta); release(S.err); release(S.names); release(S.name_off); release(S.prefix);
-  for (int k = 0; k < 2; k++) {
-    release(S.in[k]);
-    if (S.pin[k]) (void)hipHostFree(S.pin[k]);
-    if (S.ev[k]) (void)hipEventDestroy(S.ev[k]);
-    S.pin[k] = nullptr;
-    S.ev[k] = nullptr;
-  }
+  stage_release(S.stage);
   S.begun = false;
 }
 
