@@ -25,6 +25,9 @@
  *   mh_bamfile_next       pysam.AlignmentFile.fetch                      mitty/benchmarking/mq.py:61-62
  *   mh_score_add_records  mq / derr process_bam_part                     mitty/benchmarking/mq.py:50-68, derr.py:53-76
  *   mh_model_add_records  bam2illumina.process_bam_section               mitty/empirical/bam2illumina.py:17-59, 84-105
+ *   mh_cov_add_records    gc.gc_and_coverage_for_region's pileup         mitty/empirical/gc.py:37-38, 43-59
+ *   mh_cov_gc             gc.gc_and_coverage_for_region's seq.count      mitty/empirical/gc.py:32-36
+ *   mh_bq_add_records     bq.bq_over_chromosome                          mitty/empirical/bq.py:20-35
  *
  * Threading: one mh_ctx per GPU and per host thread; a context owns one HIP stream and all device buffers.
  * Calls are synchronous at return (device work is ordered on the context's stream; results copied back are
@@ -93,6 +96,10 @@ int32_t mh_work_units(uint64_t seed, const int32_t *ploidy, int64_t n_regions, i
 /* ---- reference sequence and haplotypes ----------------------------------------------------------------- */
 /* Upload (or replace) contig `contig_id` — the bytes of one BED region as fetched from the FASTA. */
 int32_t mh_upload_contig(mh_ctx *ctx, int32_t contig_id, const char *seq, int64_t len);
+/* Forget contig `contig_id` and free its device buffer (waits for the context's queued work); an id that was never
+ * uploaded is MH_OK.  Any int32 is an id: the Python engine uses the region indices 0, 1, ..., and mitty_amd's gc-cov
+ * keeps its one resident contig under a negative id. */
+int32_t mh_release_contig(mh_ctx *ctx, int32_t contig_id);
 /* Splice one chromosome copy on the device: variants (1-based pos, op 'X'/'I'/'D', oplen, alt bytes in
  * alt_pool[alt_off .. +alt_len)) applied to contig `contig_id`, whose first base has 1-based coordinate
  * ref_start_pos.  Result kept in haplotype slot `slot`.  Outputs: node count, p_min, p_max (rpc/readgenerate.py:192). */
@@ -434,6 +441,55 @@ int32_t mh_model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, cons
 int32_t mh_model_add_store(mh_ctx *ctx);
 int32_t mh_model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts);
 int32_t mh_model_reset(mh_ctx *ctx);
+
+/* ---- gc-cov (gc_and_coverage_for_region, mitty/empirical/gc.py:24-40, per block of block_len by
+ * gc_and_coverage_for_chromosome, :43-59, over the header's first 24 @SQ by process_bam_parallel, :62-78; cli.py:32-42).
+ * Contig c of length LN has blocks k = 0 .. ceil((LN - 1) / block_len) - 1 (range(1, LN, block_len)); block k is the
+ * 0-based [a, b) = [k block_len, min(k block_len + block_len + 1, LN)) (the 1-based inclusive region r-(r + block_len)).
+ * A record with tid < 0 is not visited, one with 24 <= tid < n_refs is skipped, one with flag & 0x704 is skipped (the
+ * pileup's filter), one without M/D/N/=/X operations is skipped; any other covers [pos, end), end = pos + the sum of
+ * those operations' lengths (deleted and skipped columns count).  Per block: span_sum = the sum of end - pos, min_pos
+ * and max_end over the records with pos < b and end > a; covered = the positions of [a, b) inside at least one
+ * record's interval.  tid >= n_refs, or pos outside [0, LN) of a covering record, is MH_E_ARG naming the first such
+ * record at mh_cov_result (message "gc-cov: record N: ..."; the outputs are then still filled, with the sums of the
+ * calls before the failing one); once a record fails nothing of its call or of a later one is kept.  All sums are exact and
+ * independent of the chunking; htslib's max_depth is not modelled.
+ *   mh_cov_begin        a new session: lengths[n_refs] (the header's LN), block_len >= 1, fewer than 2^31 blocks per
+ *                       contig; allocates 4 bytes per base of the first 24 contigs (twice that once a result is read)
+ *   mh_cov_add_records  as mh_score_add_records; a session takes fewer than 2^31 records (MH_E_CAPACITY)
+ *   mh_cov_add_store    the context's own BAM record store in HBM (reference lengths as mh_bam_set_refs gave them must
+ *                       be the session's); a spilled store is refused
+ *   mh_cov_gc           n_n / n_gc of contig ref_index's blocks from the uploaded contig contig_id (mh_upload_contig;
+ *                       its length must be LN): the bytes 'N', and 'G' or 'C', upper case only
+ *   mh_cov_result       waits; contig ref_index's per-block arrays (n_blocks must be its block count; any may be NULL;
+ *                       min_pos MH_COV_NO_POS and max_end 0 where no record met the block) and counts[6] = records seen,
+ *                       used, skipped for tid < 0, for tid >= 24, by flag, for no reference span.  Records may be added
+ *                       after a result.
+ *   mh_cov_reset        zero sums (n_n / n_gc included) and no error, same session parameters
+ * Unlike mh_model_result and mh_bq_result, which return nothing once a record has failed, mh_cov_result then still
+ * fills its outputs: the track and the block sums have no per-chunk copy to show that they were left alone. */
+#define MH_COV_NO_POS INT64_MAX
+int32_t mh_cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_t block_len);
+int32_t mh_cov_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t mh_cov_add_store(mh_ctx *ctx);
+int32_t mh_cov_gc(mh_ctx *ctx, int32_t ref_index, int32_t contig_id);
+int32_t mh_cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc, int64_t *covered,
+                      uint64_t *span_sum, int64_t *min_pos, int64_t *max_end, int64_t n_blocks, int64_t *counts);
+int32_t mh_cov_reset(mh_ctx *ctx);
+
+/* ---- bq (bq_over_chromosome, mitty/empirical/bq.py:20-35, per contig of the header's first 24 @SQ by
+ * process_bam_parallel, :38-54; cli.py:45-51): per contig a u64[500][100] matrix, mat[i, Q_i] += 1 over every record
+ * placed on it with flag <= 255 (whatever its 0x4 bit), Q reversed for flag & 0x10.  The passes and the failures are
+ * mh_model's (l_seq 0, l_seq > 500, a quality >= 100, tid >= n_refs: MH_E_ARG at mh_bq_result naming the first such
+ * record; nothing of its call or a later one is kept).
+ *   mh_bq_result   waits; contig ref_index's matrix and counts[8] as mh_model_result's (either may be NULL) */
+#define MH_BQ_MAX_BP 500
+#define MH_BQ_MAX_BQ 100
+int32_t mh_bq_begin(mh_ctx *ctx, int32_t n_refs);
+int32_t mh_bq_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t mh_bq_add_store(mh_ctx *ctx);
+int32_t mh_bq_result(mh_ctx *ctx, int32_t ref_index, uint64_t *mat, int64_t *counts);
+int32_t mh_bq_reset(mh_ctx *ctx);
 
 /* ---- VCF ingest (vcfio.load_variant_file / split_copies / parse, vcfio.py:51-126) ------
  * Host-only (no device): mh_vcf_open parses a plain or bgzipped VCF for one sample; mh_vcf_region runs the BED

@@ -18,7 +18,7 @@ MH_RNG_MITTY, MH_RNG_PHILOX = 0, 1
 # Every exported symbol of include/mitty_hip.h (tests check the library exports all of them).
 EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_error', 'mh_sync',
            'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort', 'mh_selftest_bgzf',
-           'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes', 'mh_get_haplotype_aux',
+           'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_release_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes', 'mh_get_haplotype_aux',
            'mh_release_haplotype', 'mh_expand_variant', 'mh_sample_templates', 'mh_sample_templates_span', 'mh_set_templates',
            'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
            'mh_read_batch', 'mh_set_corruption', 'mh_set_corruption_stream', 'mh_get_corruption_stream', 'mh_stage_times', 'mh_enable_timing', 'mh_sample_units', 'mh_sample_units_async', 'mh_templates_count',
@@ -31,10 +31,14 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_bamfile_open', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
            'mh_score_begin', 'mh_score_add_records', 'mh_score_add_store', 'mh_score_result', 'mh_score_reset',
            'mh_model_begin', 'mh_model_add_records', 'mh_model_add_store', 'mh_model_result', 'mh_model_reset',
+           'mh_cov_begin', 'mh_cov_add_records', 'mh_cov_add_store', 'mh_cov_gc', 'mh_cov_result', 'mh_cov_reset',
+           'mh_bq_begin', 'mh_bq_add_records', 'mh_bq_add_store', 'mh_bq_result', 'mh_bq_reset',
            'mh_fasta_open', 'mh_fasta_error', 'mh_fasta_count', 'mh_fasta_contig', 'mh_fasta_copy', 'mh_fasta_close']
 
 
 MODEL_NO_RLEN = (1 << 63) - 1   # MH_MODEL_NO_RLEN: counts[6] of mh_model_result when no record was used
+COV_NO_POS = (1 << 63) - 1      # MH_COV_NO_POS: min_pos of a block no record met
+BQ_MAX_BP, BQ_MAX_BQ = 500, 100   # MH_BQ_MAX_BP, MH_BQ_MAX_BQ: bq.py:28
 
 
 class NativeError(RuntimeError):
@@ -84,6 +88,7 @@ def lib():
   _sig(L, 'mh_read_model_params', [c_i64, c_dbl, ctypes.POINTER(c_dbl), P_i64])
   _sig(L, 'mh_work_units', [c_u64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, P_i64])
   _sig(L, 'mh_upload_contig', [c_vp, c_i32, c_vp, c_i64])
+  _sig(L, 'mh_release_contig', [c_vp, c_i32])
   _sig(L, 'mh_upload_variants', [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64])
   _sig(L, 'mh_build_haplotype_vset', [c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp])
   _sig(L, 'mh_release_variants', [c_vp, c_i32])
@@ -164,6 +169,17 @@ def lib():
   _sig(L, 'mh_model_add_store', [c_vp])
   _sig(L, 'mh_model_result', [c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_model_reset', [c_vp])
+  _sig(L, 'mh_cov_begin', [c_vp, c_i32, c_vp, c_i64])
+  _sig(L, 'mh_cov_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
+  _sig(L, 'mh_cov_add_store', [c_vp])
+  _sig(L, 'mh_cov_gc', [c_vp, c_i32, c_i32])
+  _sig(L, 'mh_cov_result', [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp])
+  _sig(L, 'mh_cov_reset', [c_vp])
+  _sig(L, 'mh_bq_begin', [c_vp, c_i32])
+  _sig(L, 'mh_bq_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
+  _sig(L, 'mh_bq_add_store', [c_vp])
+  _sig(L, 'mh_bq_result', [c_vp, c_i32, c_vp, c_vp])
+  _sig(L, 'mh_bq_reset', [c_vp])
   _sig(L, 'mh_fasta_open', [ctypes.c_char_p, c_vp, ctypes.POINTER(c_vp)])
   _sig(L, 'mh_fasta_error', [c_vp], ctypes.c_char_p)
   _sig(L, 'mh_fasta_count', [c_vp, ctypes.POINTER(c_i32)])
@@ -525,6 +541,10 @@ class Context:
   def upload_contig(self, contig_id, seq):
     buf = np.frombuffer(seq, dtype=np.uint8) if len(seq) else np.zeros(1, np.uint8)
     self._chk(self._L.mh_upload_contig(self._h, contig_id, _ptr(buf), len(seq)))
+
+  def release_contig(self, contig_id):
+    """Forget an uploaded contig and free its device buffer."""
+    self._chk(self._L.mh_release_contig(self._h, int(contig_id)))
 
   def build_haplotype(self, slot, contig_id, ref_start_pos, vsoa):
     """vsoa: dict with pos i64, op u8, oplen i64, alt_off i64, alt_len i64, alt_pool bytes."""
@@ -1031,6 +1051,88 @@ class Context:
 
   def model_reset(self):
     self._chk(self._L.mh_model_reset(self._h))
+
+  # ---- gc-cov: depth, block sums, GC / N counts ----
+  def cov_begin(self, lengths, block_len=10000):
+    """A new gc-cov session over a BAM whose header lists the references of these lengths (the first 24 are
+    visited)."""
+    ln = np.ascontiguousarray(lengths, dtype=np.int64)
+    self._chk(self._L.mh_cov_begin(self._h, len(ln), _ptr(ln) if len(ln) else None, int(block_len)))
+    bl = int(block_len)
+    self._cov_blocks = [len(range(1, int(x), bl)) for x in ln[:24]]
+
+  def cov_add_raw(self, recs_addr, nbytes, roff_addr, n):
+    """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by cov_result."""
+    self._chk(self._L.mh_cov_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+
+  def cov_add_records(self, recs, roff):
+    """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
+    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
+    o = np.ascontiguousarray(roff, dtype=np.int64)
+    self._chk(self._L.mh_cov_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+
+  def cov_add_store(self):
+    """The context's own BAM record store (bam_add_fastq / bam_add_output) through the session, in HBM."""
+    self._chk(self._L.mh_cov_add_store(self._h))
+
+  def cov_gc(self, ref_index, contig_id):
+    """Count N and G/C of the uploaded contig `contig_id` into the blocks of the header's contig `ref_index`."""
+    self._chk(self._L.mh_cov_gc(self._h, int(ref_index), int(contig_id)))
+
+  def cov_result(self, ref_index, failed_ok=False):
+    """(per-block dict of contig ref_index, counts dict).  Arrays: n_n, n_gc (u32), covered, min_pos, max_end (i64),
+    span_sum (u64); min_pos is COV_NO_POS and max_end 0 where no record met the block.  failed_ok: a session with a
+    failed record does not raise; a third value is its message (else None), the sums are those before the failing
+    call."""
+    nb = self._cov_blocks[ref_index]
+    m = max(nb, 1)
+    out = {'n_n': np.zeros(m, np.uint32), 'n_gc': np.zeros(m, np.uint32), 'covered': np.zeros(m, np.int64),
+           'span_sum': np.zeros(m, np.uint64), 'min_pos': np.zeros(m, np.int64), 'max_end': np.zeros(m, np.int64)}
+    cnt = np.zeros(6, np.int64)
+    rc = self._L.mh_cov_result(self._h, int(ref_index), _ptr(out['n_n']), _ptr(out['n_gc']), _ptr(out['covered']),
+                               _ptr(out['span_sum']), _ptr(out['min_pos']), _ptr(out['max_end']), nb, _ptr(cnt))
+    failed = None
+    if rc:
+      failed = self._L.mh_last_error(self._h).decode(errors='replace')
+      if not (failed_ok and rc == MH_E_ARG and failed.startswith('gc-cov: record ')):
+        _raise(rc, failed)
+    res = ({k: v[:nb] for k, v in out.items()},
+           dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_flag', 'skipped_nospan'),
+                    (int(x) for x in cnt))))
+    return res + (failed,) if failed_ok else res
+
+  def cov_reset(self):
+    self._chk(self._L.mh_cov_reset(self._h))
+
+  # ---- bq: base qualities per contig ----
+  def bq_begin(self, n_refs):
+    """A new bq session over a BAM whose header lists n_refs references (the first 24 are visited)."""
+    self._chk(self._L.mh_bq_begin(self._h, int(n_refs)))
+
+  def bq_add_raw(self, recs_addr, nbytes, roff_addr, n):
+    self._chk(self._L.mh_bq_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+
+  def bq_add_records(self, recs, roff):
+    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
+    o = np.ascontiguousarray(roff, dtype=np.int64)
+    self._chk(self._L.mh_bq_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+
+  def bq_add_store(self):
+    self._chk(self._L.mh_bq_add_store(self._h))
+
+  def bq_result(self, ref_index):
+    """(u64[500, 100] matrix of contig ref_index, counts dict as model_result's)."""
+    mat = np.zeros((BQ_MAX_BP, BQ_MAX_BQ), np.uint64)
+    cnt = np.zeros(8, np.int64)
+    self._chk(self._L.mh_bq_result(self._h, int(ref_index), _ptr(mat), _ptr(cnt)))
+    d = dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_every', 'skipped_flag', 'min_rlen',
+                  'max_rlen'), (int(x) for x in cnt)))
+    if d['min_rlen'] == MODEL_NO_RLEN:
+      d['min_rlen'] = None
+    return mat, d
+
+  def bq_reset(self):
+    self._chk(self._L.mh_bq_reset(self._h))
 
   def bam_partition(self, splitters, tie_base):
     """The store's records by destination rank (mh_bam_partition): returns (segment offsets [n_dest + 1], records

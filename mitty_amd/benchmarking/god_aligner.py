@@ -81,6 +81,24 @@ def header_text(hdr, sorted_by='coordinate'):
   return '\n'.join(lines) + '\n'
 
 
+def seq_info(text, names=None, lengths=None):
+  """The @SQ lines of SAM header text the way pysam's header['SQ'] holds them: one dict per line in header order, tags
+  in line order, LN an int, every other value a str.  A header without @SQ text: SN and LN of the BAM's own reference
+  list (names, lengths), as htslib makes them up."""
+  sq = []
+  for line in text.split('\n'):
+    if not line.startswith('@SQ\t'):
+      continue
+    d = {}
+    for field in line.rstrip('\r').split('\t')[1:]:
+      k, _, v = field.partition(':')
+      d[k] = int(v) if k == 'LN' else v
+    sq.append(d)
+  if not sq and names is not None:
+    sq = [{'SN': n, 'LN': int(ln)} for n, ln in zip(names, lengths)]
+  return sq
+
+
 def process_multi_threaded(fasta, bam_fname, fastq1, fastq2=None, threads=1, max_templates=None,
                            sample_name='Seven', device=0, level=6, chunk_bytes=1 << 30, gpu_bgzf=False,
                            hbm_capacity=0):

@@ -1,12 +1,13 @@
 """`mitty` command line (reference mitty/cli.py), MI355X build.
 
 Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), mq-plot and derr-plot (GPU scoring, host
-BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; additive --device), filter-variants
+BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; additive --device), gc-cov and bq (GPU
+depth track, block sums and histograms, host BAM reader; additive --device), filter-variants
 (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
 --rng {mitty,philox}, --corrupt-seed (fused Philox corruption); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
 RCCL); the output files are identical to the one-GPU run.  Out of scope for this build (not on the
-generate-reads path): filter-bam, gc-cov, bq, describe-read-model.
+generate-reads path): filter-bam (a stub in the reference), describe-read-model (plotting only).
 """
 import logging
 import os
@@ -32,6 +33,30 @@ def filter_vcf(vcfin, sample, bed, vcfout):
    making it suitable to use for read generation (reference cli.py:20-35)"""
   from mitty_amd.lib import vcfio
   vcfio.prepare_variant_file(vcfin, sample, bed, vcfout)
+
+
+@cli.command('gc-cov')
+@click.argument('bam', type=click.Path(exists=True))
+@click.argument('fasta', type=click.Path(exists=True))
+@click.argument('pkl')
+@click.option('-b', '--block-len', type=int, default=10000, help='Block size for GC/cov computation')
+@click.option('-t', '--threads', type=int, default=1, help='Threads to use')
+@click.option('--device', default=0, help='HIP device ordinal')
+def gc_cov(bam, fasta, pkl, block_len, threads, device):
+  """Calculate GC content vs coverage from a BAM. Save in pickle file (reference cli.py:32-42)"""
+  from mitty_amd.empirical import gc
+  gc.process_bam_parallel(bam, fasta, pkl, block_len=block_len, threads=threads, device=device)
+
+
+@cli.command('bq')
+@click.argument('bam', type=click.Path(exists=True))
+@click.argument('pkl')
+@click.option('-t', '--threads', type=int, default=1, help='Threads to use')
+@click.option('--device', default=0, help='HIP device ordinal')
+def sample_bq(bam, pkl, threads, device):
+  """BQ distribution from BAM (reference cli.py:45-51)"""
+  from mitty_amd.empirical import bq
+  bq.process_bam_parallel(bam, pkl, threads=threads, device=device)
 
 
 @cli.command('bam2illumina', short_help='Create read model from BAM file')

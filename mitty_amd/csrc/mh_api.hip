@@ -546,6 +546,8 @@ int32_t mh_destroy(mh_ctx *ctx) {
   bam_release(ctx->bam);
   score_release(ctx->score);
   model_release(ctx->model);
+  model_release(ctx->bq);
+  cov_release(ctx->cov);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -733,6 +735,16 @@ int32_t mh_upload_contig(mh_ctx *ctx, int32_t contig_id, const char *seq, int64_
   if (len) HIPCHK(ctx, hipMemcpyAsync(c.seq.p, seq, len, hipMemcpyHostToDevice, ctx->stream));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
   c.len = len;
+  return MH_OK;
+}
+
+int32_t mh_release_contig(mh_ctx *ctx, int32_t contig_id) {
+  CTX_GUARD(ctx);
+  auto it = ctx->contigs.find(contig_id);
+  if (it == ctx->contigs.end()) return MH_OK;
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  release(it->second.seq);
+  ctx->contigs.erase(it);
   return MH_OK;
 }
 
@@ -1851,28 +1863,89 @@ int32_t mh_score_reset(mh_ctx *ctx) {
 int32_t mh_model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
                        int32_t max_tlen) {
   CTX_GUARD(ctx);
-  return model_begin(ctx, n_refs, every, min_mq, max_bq, max_bp, max_tlen);
+  return model_begin(ctx, ctx->model, n_refs, every, min_mq, max_bq, max_bp, max_tlen, false);
 }
 
 int32_t mh_model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   CTX_GUARD(ctx);
   if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
-  return model_add_records(ctx, recs, len, roff, n);
+  return model_add_records(ctx, ctx->model, recs, len, roff, n);
 }
 
 int32_t mh_model_add_store(mh_ctx *ctx) {
   CTX_GUARD(ctx);
-  return model_add_store(ctx);
+  return model_add_store(ctx, ctx->model);
 }
 
 int32_t mh_model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts) {
   CTX_GUARD(ctx);
-  return model_result(ctx, bq_mat, tlen_mat, counts);
+  return model_result(ctx, ctx->model, bq_mat, tlen_mat, counts);
 }
 
 int32_t mh_model_reset(mh_ctx *ctx) {
   CTX_GUARD(ctx);
-  return model_reset(ctx);
+  return model_reset(ctx, ctx->model);
+}
+
+// ---- bq: base qualities per contig (mh_model.hip's passes, a table per contig) ------------------------------------
+int32_t mh_bq_begin(mh_ctx *ctx, int32_t n_refs) {
+  CTX_GUARD(ctx);
+  return model_begin(ctx, ctx->bq, n_refs, 1, 0, MH_BQ_MAX_BQ, MH_BQ_MAX_BP, 1, true);
+}
+
+int32_t mh_bq_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  CTX_GUARD(ctx);
+  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  return model_add_records(ctx, ctx->bq, recs, len, roff, n);
+}
+
+int32_t mh_bq_add_store(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return model_add_store(ctx, ctx->bq);
+}
+
+int32_t mh_bq_result(mh_ctx *ctx, int32_t ref_index, uint64_t *mat, int64_t *counts) {
+  CTX_GUARD(ctx);
+  return model_result_table(ctx, ctx->bq, ref_index, mat, counts);
+}
+
+int32_t mh_bq_reset(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return model_reset(ctx, ctx->bq);
+}
+
+// ---- gc-cov: depth track, block sums, GC / N counts (mh_cov.hip) --------------------------------------------------
+int32_t mh_cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_t block_len) {
+  CTX_GUARD(ctx);
+  if (n_refs < 0 || (n_refs > 0 && !lengths)) return arg_fail(ctx, MH_E_ARG, "bad reference list");
+  return cov_begin(ctx, n_refs, lengths, block_len);
+}
+
+int32_t mh_cov_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  CTX_GUARD(ctx);
+  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  return cov_add_records(ctx, recs, len, roff, n);
+}
+
+int32_t mh_cov_add_store(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return cov_add_store(ctx);
+}
+
+int32_t mh_cov_gc(mh_ctx *ctx, int32_t ref_index, int32_t contig_id) {
+  CTX_GUARD(ctx);
+  return cov_gc(ctx, ref_index, contig_id);
+}
+
+int32_t mh_cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc, int64_t *covered,
+                      uint64_t *span_sum, int64_t *min_pos, int64_t *max_end, int64_t n_blocks, int64_t *counts) {
+  CTX_GUARD(ctx);
+  return cov_result(ctx, ref_index, n_n, n_gc, covered, span_sum, min_pos, max_end, n_blocks, counts);
+}
+
+int32_t mh_cov_reset(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return cov_reset(ctx);
 }
 
 }  // extern "C"

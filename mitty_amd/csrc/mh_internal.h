@@ -220,7 +220,7 @@ struct BamStore {
 };
 
 // Host BAM records on their way to the device, shared by the sessions that take records from the host reader
-// (mh_score.hip, mh_model.hip): two page-locked buffers, so chunk k + 1 is checked and copied while chunk k is worked on.
+// (mh_score.hip, mh_model.hip, mh_cov.hip): two page-locked buffers, so chunk k + 1 is checked and copied while chunk k is worked on.
 struct RecStage {
   DevBuf in[2];                // the chunk on the device: record offsets, then the records
   uint8_t *pin[2] = {nullptr, nullptr};   // page-locked staging, one per chunk in flight
@@ -248,18 +248,41 @@ struct ScoreState {
   int64_t base_rec = 0;        // records given to earlier calls (names a failing record)
 };
 
-// Read-model builder (mh_model.hip, bam2illumina): the session's histograms, resident until read back.
+// Read-model builder (mh_model.hip, bam2illumina): the session's histograms, resident until read back.  The `bq`
+// session is a second one whose tables are the visited contigs (by_ref) instead of the mates.
 struct ModelState {
   static constexpr int N_REF = 24;   // refs[:24]: only the header's first 24 @SQ are visited
   bool begun = false;
   int32_t n_refs = 0, every = 1, min_mq = 0, max_bq = 0, max_bp = 0, max_tlen = 0;
-  int32_t slab_bp = 0, n_slab = 0;   // base positions per LDS table, tables per mate
+  int32_t n_tab = 2;                 // bq tables: the two mates, or N_REF contigs (by_ref)
+  bool by_ref = false;
+  int32_t slab_bp = 0, n_slab = 0;   // base positions per LDS table, LDS tables per bq table
   int64_t n_bq = 0, n_all = 0;       // u64 cells of bq_mat; of everything
   // [bq_mat | tlen | 6 counts, INT32_MAX - min_rlen, max_rlen | records per refID (N_REF)]: the session's / the chunk's
   DevBuf acc, delta;
   DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
   DevBuf desc;                 // per record of the chunk: where its qualities are, l_seq, mate and strand
   DevBuf tile_ord;             // every > 1: per 256-record tile and refID the ordinal of the tile's first such record
+  RecStage stage;
+  int64_t base_rec = 0;
+};
+
+// gc-cov (mh_cov.hip): the depth track over the visited contigs and the per-block sums of one session.
+struct CovState {
+  static constexpr int N_REF = ModelState::N_REF;
+  bool begun = false;
+  int32_t n_refs = 0, n_vis = 0;
+  int64_t block_len = 0;
+  int64_t ln[N_REF] = {0}, cbase[N_REF + 1] = {0}, bbase[N_REF + 1] = {0};   // lengths; first cell / block of a contig
+  int64_t n_cells = 0, n_blk = 0;   // contig c owns ln[c] + 1 cells of the track and bbase[c + 1] - bbase[c] blocks
+  DevBuf track, depth;         // i32 per cell: +1 at pos, -1 at min(end, LN); its inclusive scan (at result)
+  DevBuf blk;                  // per block: span sum u64 | min pos u64 | max end u64 | covered i64 | nN u32 | nGC u32
+  DevBuf cnt;                  // u64[6]: seen, used, skipped unplaced / ref / flag / nospan
+  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
+  DevBuf desc;                 // per record of the chunk: class, contig, pos, end
+  DevBuf partials;             // the scan's
+  DevBuf tab;                  // i64: ln[N_REF] | cbase[N_REF + 1] | bbase[N_REF + 1] for the kernels
+  bool scanned = false;        // depth and the covered counts hold the track as it is now
   RecStage stage;
   int64_t base_rec = 0;
 };
@@ -434,8 +457,10 @@ struct mh_ctx {
   mh::BamStore bam;
   // mq-plot / derr-plot scoring session
   mh::ScoreState score;
-  // bam2illumina session
-  mh::ModelState model;
+  // bam2illumina session; bq session (the same passes, a table per contig)
+  mh::ModelState model, bq;
+  // gc-cov session
+  mh::CovState cov;
 };
 
 namespace mh {
@@ -614,13 +639,24 @@ int32_t stage_queued(mh_ctx *ctx, RecStage &G, int slot);
 int32_t stage_init(mh_ctx *ctx, RecStage &G);   // its events exist; the chunks in flight are done
 void stage_release(RecStage &G);
 // read-model histograms (mh_model.hip)
-int32_t model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
-                    int32_t max_tlen);
-int32_t model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
-int32_t model_add_store(mh_ctx *ctx);
-int32_t model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts);
-int32_t model_reset(mh_ctx *ctx);
+int32_t model_begin(mh_ctx *ctx, ModelState &S, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq,
+                    int32_t max_bp, int32_t max_tlen, bool by_ref);
+int32_t model_add_records(mh_ctx *ctx, ModelState &S, const uint8_t *recs, int64_t len, const int64_t *roff,
+                          int64_t n);
+int32_t model_add_store(mh_ctx *ctx, ModelState &S);
+int32_t model_result(mh_ctx *ctx, ModelState &S, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts);
+int32_t model_result_table(mh_ctx *ctx, ModelState &S, int32_t tab, uint64_t *mat, int64_t *counts);
+int32_t model_reset(mh_ctx *ctx, ModelState &S);
 void model_release(ModelState &S);
+// depth track and block sums (mh_cov.hip)
+int32_t cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_t block_len);
+int32_t cov_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t cov_add_store(mh_ctx *ctx);
+int32_t cov_gc(mh_ctx *ctx, int32_t ref_index, int32_t contig_id);
+int32_t cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc, int64_t *covered, uint64_t *span_sum,
+                   int64_t *min_pos, int64_t *max_end, int64_t n_blocks, int64_t *counts);
+int32_t cov_reset(mh_ctx *ctx);
+void cov_release(CovState &S);
 int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_t *d1, int64_t len1, int64_t t_base,
                       int64_t *used0, int64_t *used1, int64_t *templates);
 

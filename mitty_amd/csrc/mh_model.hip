@@ -10,6 +10,9 @@
 //                  bq[position][quality] of ONE mate; flushed once per workgroup with 64-bit global atomics
 //     -> k_model_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
 //
+// The same passes serve `bq` (reference mitty/empirical/bq.py:20-35, per contig by :38-54): a second ModelState whose
+// table selector is the record's refID instead of its mate (by_ref), 24 tables of 500 x 100, no template lengths.
+//
 // LDS split: 2 x 300 x 94 x 4 B = 225 KB does not fit the CU's 160 KiB, one mate's 112.8 KB does.  A workgroup of 1024
 // threads owns a 120 KiB table and takes the records of one mate (blockIdx chooses it); it skips the other mate's
 // records by their descriptors, so no quality byte is loaded twice.  A shape whose mate table exceeds 120 KiB (max_bq
@@ -40,7 +43,7 @@ enum { ME_STRUCT = 1, ME_TID = 2, ME_EMPTY = 3, ME_LONG = 4, ME_QUAL = 5 };
 struct ModelDesc {   // 16 bytes per record of the chunk
   int64_t q;         // offset of the qualities from recs; -1: the record is not used
   int32_t len;       // l_seq
-  int32_t bits;      // bit 0: mate index m (0: read1), bit 1: reverse strand
+  int32_t bits;      // bit 0: reverse strand; bits 1..: the table (mate index m, 0: read1; by_ref: the refID)
 };
 
 struct ModelArgs {
@@ -48,7 +51,7 @@ struct ModelArgs {
   const int64_t *roff;
   int64_t n, avail;
   int32_t n_refs, every, min_mq, max_bq, max_bp, max_tlen;
-  int32_t slab_bp, n_slab, wg_per_part;
+  int32_t slab_bp, n_slab, wg_per_part, by_ref;
   unsigned long long *bq, *tlen, *cnt, *refcnt;   // the chunk's sums
   const unsigned long long *ref_base;             // the session's records per refID before this chunk
   unsigned long long *tile_ord;                   // [tiles][MD_REF]
@@ -180,7 +183,7 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
             L = (int32_t)l_seq;
             d.q = s + qoff;
             d.len = L;
-            d.bits = ((flag & 0x40) ? 0 : 1) | ((flag & 0x10) ? 2 : 0);
+            d.bits = (a.by_ref ? tid : ((flag & 0x40) ? 0 : 1)) << 1 | ((flag & 0x10) ? 1 : 0);
             int64_t T = (int64_t)(int32_t)md32(p + 32);
             if (T < 0) T = -T;
             if (mapq >= a.min_mq && mapq != 255 && (flag & 0x80) && T < a.max_tlen) tcell = (int32_t)T;
@@ -227,13 +230,13 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
     atomicMax(&a.cnt[threadIdx.x], (unsigned long long)l_cnt[threadIdx.x]);
 }
 
-// blockIdx.x = part * wg_per_part + g; part = mate * n_slab + slab.  The part's workgroups share the chunk's records in
+// blockIdx.x = part * wg_per_part + g; part = table * n_slab + slab.  The part's workgroups share the chunk's records in
 // batches of 64 descriptors per wave.
 __global__ void __launch_bounds__(1024) k_model_hist(ModelArgs a) {
   __shared__ uint32_t tab[MD_LDS_CELLS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int part = blockIdx.x / a.wg_per_part, g = blockIdx.x - part * a.wg_per_part;
-  const int mate = part / a.n_slab, slab = part - mate * a.n_slab;
+  const int tsel = part / a.n_slab, slab = part - tsel * a.n_slab;
   const int32_t p0 = slab * a.slab_bp, p1 = min(p0 + a.slab_bp, a.max_bp);
   const int32_t cells = (p1 - p0) * a.max_bq;   // <= MD_LDS_CELLS (model_begin)
   for (int i = threadIdx.x; i < cells; i += 1024) tab[i] = 0;
@@ -243,12 +246,12 @@ __global__ void __launch_bounds__(1024) k_model_hist(ModelArgs a) {
     const int64_t r = batch * 64 + lane;
     ModelDesc d{-1, 0, 0};
     if (r < a.n) d = a.desc[r];
-    uint64_t pend = __ballot(d.q >= 0 && (d.bits & 1) == mate && d.len > p0);
+    uint64_t pend = __ballot(d.q >= 0 && (d.bits >> 1) == tsel && d.len > p0);
     while (pend) {
       const int j = __ffsll((unsigned long long)pend) - 1;
       pend &= pend - 1;
       const int64_t q = __shfl(d.q, j, 64);
-      const int32_t len = __shfl(d.len, j, 64), rev = __shfl(d.bits, j, 64) & 2;
+      const int32_t len = __shfl(d.len, j, 64), rev = __shfl(d.bits, j, 64) & 1;
       const int32_t hi = min(len, p1);
       for (int32_t i0 = p0 + lane; i0 < hi; i0 += 256) {   // (no barrier or shuffle inside: lanes past the end leave)
         uint32_t b[4];   // up to 256 positions' bytes in flight before the first add
@@ -269,7 +272,7 @@ __global__ void __launch_bounds__(1024) k_model_hist(ModelArgs a) {
     }
   }
   __syncthreads();
-  unsigned long long *out = a.bq + ((int64_t)mate * a.max_bp + p0) * a.max_bq;
+  unsigned long long *out = a.bq + ((int64_t)tsel * a.max_bp + p0) * a.max_bq;
   for (int i = threadIdx.x; i < cells; i += 1024)
     if (tab[i]) atomicAdd(&out[i], (unsigned long long)tab[i]);
 }
@@ -286,8 +289,8 @@ __global__ void k_model_commit(const unsigned long long *delta, unsigned long lo
 }
 
 // the chunk's sums zeroed, the passes over the records, the sums committed; all queued on the context's stream
-int32_t model_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail, int32_t n_refs) {
-  ModelState &S = ctx->model;
+int32_t model_launch(mh_ctx *ctx, ModelState &S, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail,
+                     int32_t n_refs) {
   hipStream_t st = ctx->stream;
   const int64_t tiles = (n + 255) / 256;
   MH_TRY(ensure(ctx, S.desc, sizeof(ModelDesc) * (size_t)n));
@@ -295,15 +298,19 @@ int32_t model_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int6
   HIPCHK(ctx, hipMemsetAsync(S.delta.p, 0, sizeof(uint64_t) * S.n_all, st));
   unsigned long long *d = (unsigned long long *)S.delta.p;
   const int64_t o_tlen = S.n_bq, o_cnt = o_tlen + S.max_tlen, o_ref = o_cnt + MD_NCNT;
-  const int parts = 2 * S.n_slab;
+  const int parts = S.n_tab * S.n_slab;
   // a part's workgroups: enough for every CU, no more than there are 16-wave loads of 64 records; 32-bit LDS counters
   // gain 1 per record at the most, so fewer than 2^32 records per workgroup
+  // by_ref: a chunk's records sit on one or two contigs (a sorted file, a one-contig store), so a table's share is
+  // sized as if it had the device alone; the other tables' workgroups find no record of theirs and flush nothing
   const int64_t batches = (n + 63) / 64;
-  int64_t wgp = std::min<int64_t>((batches + 15) / 16, std::max<int64_t>(1, (ctx->max_cu + parts - 1) / parts));
+  const int busy = S.by_ref ? S.n_slab : parts;
+  int64_t wgp = std::min<int64_t>((batches + 15) / 16, std::max<int64_t>(1, (ctx->max_cu + busy - 1) / busy));
   wgp = std::max<int64_t>(wgp, (n >> 31) + 1);
   ModelArgs a{recs, roff, n, avail, n_refs, S.every, S.min_mq, S.max_bq, S.max_bp, S.max_tlen, S.slab_bp, S.n_slab,
-              (int32_t)wgp, d, d + o_tlen, d + o_cnt, d + o_ref, (const unsigned long long *)S.acc.p + o_ref,
-              (unsigned long long *)S.tile_ord.p, (ModelDesc *)S.desc.p, (unsigned long long *)S.err.p, S.base_rec};
+              (int32_t)wgp, S.by_ref ? 1 : 0, d, d + o_tlen, d + o_cnt, d + o_ref,
+              (const unsigned long long *)S.acc.p + o_ref, (unsigned long long *)S.tile_ord.p,
+              (ModelDesc *)S.desc.p, (unsigned long long *)S.err.p, S.base_rec};
   const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
   if (S.every > 1) {
     hipLaunchKernelGGL(k_model_refcount, dim3((unsigned)grid), dim3(256), 0, st, a);
@@ -323,8 +330,7 @@ int32_t model_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int6
   return MH_OK;
 }
 
-int32_t model_clear(mh_ctx *ctx) {
-  ModelState &S = ctx->model;
+int32_t model_clear(mh_ctx *ctx, ModelState &S) {
   MH_TRY(stage_init(ctx, S.stage));
   HIPCHK(ctx, hipMemsetAsync(S.acc.p, 0, sizeof(uint64_t) * S.n_all, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, ctx->stream));
@@ -335,14 +341,14 @@ int32_t model_clear(mh_ctx *ctx) {
 
 }  // namespace
 
-int32_t model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq, int32_t max_bp,
-                    int32_t max_tlen) {
-  ModelState &S = ctx->model;
+int32_t model_begin(mh_ctx *ctx, ModelState &S, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq,
+                    int32_t max_bp, int32_t max_tlen, bool by_ref) {
+  const int32_t n_tab = by_ref ? MD_REF : 2;
   if (n_refs < 0) return arg_fail(ctx, MH_E_ARG, "bad reference count");
   if (every < 1) return arg_fail(ctx, MH_E_ARG, "every must be at least 1");
   if (max_bq < 1 || max_bq > 256) return arg_fail(ctx, MH_E_ARG, "max_bq must be 1..256");
   if (max_bp < 1 || max_tlen < 1) return arg_fail(ctx, MH_E_ARG, "max_bp and max_tlen must be positive");
-  if (2 * (int64_t)max_bp * max_bq >= INT32_MAX) return arg_fail(ctx, MH_E_ARG, "bq_mat of 2^31 cells or more");
+  if (n_tab * (int64_t)max_bp * max_bq >= INT32_MAX) return arg_fail(ctx, MH_E_ARG, "bq_mat of 2^31 cells or more");
   if (max_tlen == INT32_MAX) return arg_fail(ctx, MH_E_ARG, "tlen histogram of 2^31 cells or more");
   S.begun = false;
   S.n_refs = n_refs;
@@ -351,33 +357,34 @@ int32_t model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_mq, 
   S.max_bq = max_bq;
   S.max_bp = max_bp;
   S.max_tlen = max_tlen;
+  S.n_tab = n_tab;
+  S.by_ref = by_ref;
   S.slab_bp = std::min(max_bp, MD_LDS_CELLS / max_bq);
   S.n_slab = (max_bp + S.slab_bp - 1) / S.slab_bp;
-  S.n_bq = 2 * (int64_t)max_bp * max_bq;
+  S.n_bq = n_tab * (int64_t)max_bp * max_bq;
   S.n_all = S.n_bq + max_tlen + MD_NCNT + MD_REF;
   MH_TRY(stage_init(ctx, S.stage));
   MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.err, 64));
-  MH_TRY(model_clear(ctx));
+  MH_TRY(model_clear(ctx, S));
   S.begun = true;
   return MH_OK;
 }
 
-int32_t model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
-  ModelState &S = ctx->model;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_model_begin first");
+int32_t model_add_records(mh_ctx *ctx, ModelState &S, const uint8_t *recs, int64_t len, const int64_t *roff,
+                          int64_t n) {
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
   if (n == 0) return MH_OK;
   StagedRecs d;
   MH_TRY(stage_records(ctx, S.stage, recs, len, roff, n, S.base_rec, &d));
-  MH_TRY(model_launch(ctx, d.recs, d.roff, n, d.avail, S.n_refs));
+  MH_TRY(model_launch(ctx, S, d.recs, d.roff, n, d.avail, S.n_refs));
   return stage_queued(ctx, S.stage, d.slot);
 }
 
-int32_t model_add_store(mh_ctx *ctx) {
-  ModelState &S = ctx->model;
+int32_t model_add_store(mh_ctx *ctx, ModelState &S) {
   BamStore &B = ctx->bam;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_model_begin first");
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
   if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
   if (B.n_rec == 0) return MH_OK;
   if (B.spilled > 0)
@@ -385,14 +392,14 @@ int32_t model_add_store(mh_ctx *ctx) {
   // the store's own order stands for the file's: input order, or coordinate order after a direct sorted write
   const uint8_t *recs = (const uint8_t *)(B.direct ? B.srecs.p : B.recs.p);
   const int64_t *roff = (const int64_t *)(B.direct ? B.soff.p : B.roff.p);
-  MH_TRY(model_launch(ctx, recs, roff, B.n_rec, B.bytes, (int32_t)B.ref_names.size()));
+  MH_TRY(model_launch(ctx, S, recs, roff, B.n_rec, B.bytes, (int32_t)B.ref_names.size()));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
   return MH_OK;
 }
 
-int32_t model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts) {
-  ModelState &S = ctx->model;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_model_begin first");
+// the session's work waited for; the first failing record, if any, as MH_E_ARG
+static int32_t model_wait(mh_ctx *ctx, ModelState &S) {
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
   uint64_t herr = 0;
   HIPCHK(ctx, hipMemcpyAsync(&herr, S.err.p, 8, hipMemcpyDeviceToHost, ctx->stream));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -401,9 +408,15 @@ int32_t model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t 
                                  "l_seq is 0 (no qualities)", "read longer than max_bp",
                                  "base quality of max_bq or more (0xff: no qualities stored)"};
     const int kind = (int)(herr & 15);
-    return arg_fail(ctx, MH_E_ARG, "read model: record " + std::to_string(herr >> 4) + ": " +
+    return arg_fail(ctx, MH_E_ARG, std::string(S.by_ref ? "bq" : "read model") + ": record " +
+                                       std::to_string(herr >> 4) + ": " +
                                        (kind >= 1 && kind <= 5 ? what[kind] : "unknown failure"));
   }
+  return MH_OK;
+}
+
+int32_t model_result(mh_ctx *ctx, ModelState &S, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts) {
+  MH_TRY(model_wait(ctx, S));
   const uint64_t *acc = (const uint64_t *)S.acc.p;
   if (bq_mat) HIPCHK(ctx, hipMemcpyAsync(bq_mat, acc, 8 * S.n_bq, hipMemcpyDeviceToHost, ctx->stream));
   if (tlen_mat)
@@ -415,9 +428,24 @@ int32_t model_result(mh_ctx *ctx, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t 
   return MH_OK;
 }
 
-int32_t model_reset(mh_ctx *ctx) {
-  if (!ctx->model.begun) return arg_fail(ctx, MH_E_STATE, "call mh_model_begin first");
-  return model_clear(ctx);
+// one table (a contig's matrix of a by_ref session) and the counts
+int32_t model_result_table(mh_ctx *ctx, ModelState &S, int32_t tab, uint64_t *mat, int64_t *counts) {
+  MH_TRY(model_wait(ctx, S));
+  if (tab < 0 || tab >= S.n_tab || (S.by_ref && tab >= S.n_refs))
+    return arg_fail(ctx, MH_E_ARG, "no such table in the session");
+  const uint64_t *acc = (const uint64_t *)S.acc.p;
+  const int64_t cells = (int64_t)S.max_bp * S.max_bq;
+  if (mat) HIPCHK(ctx, hipMemcpyAsync(mat, acc + tab * cells, 8 * cells, hipMemcpyDeviceToHost, ctx->stream));
+  if (counts)
+    HIPCHK(ctx, hipMemcpyAsync(counts, acc + S.n_bq + S.max_tlen, 8 * MD_NCNT, hipMemcpyDeviceToHost, ctx->stream));
+  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (counts) counts[6] = counts[6] ? (int64_t)INT32_MAX - counts[6] : MH_MODEL_NO_RLEN;
+  return MH_OK;
+}
+
+int32_t model_reset(mh_ctx *ctx, ModelState &S) {
+  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
+  return model_clear(ctx, S);
 }
 
 void model_release(ModelState &S) {

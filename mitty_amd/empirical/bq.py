@@ -1,0 +1,63 @@
+"""bq: the base-quality distribution per contig of a BAM (reference mitty/empirical/bq.py).  The per-record loop
+(:28-33, per contig of the header's first 24 by :38-54) runs on the device: the host reader streams the file
+(mh_bamread.cpp) into the read model's histogram pass with a table per contig (mh_model.hip)."""
+import logging
+import pickle
+import time
+
+from mitty_amd import _native
+from mitty_amd.benchmarking.god_aligner import seq_info
+
+logger = logging.getLogger(__name__)
+
+CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
+MAX_CHROMS = 24          # (:42)
+
+
+def _results(ctx, sq):
+  bq_data = {'seq_info': sq}
+  counts = None
+  for i, s in enumerate(sq[:MAX_CHROMS]):
+    bq_data[s['SN']], counts = ctx.bq_result(i)
+  return bq_data, counts
+
+
+def count_bam(bam_fname, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
+  """(bq_data dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1."""
+  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)))
+  try:
+    sq = seq_info(bam.text, bam.names, bam.lengths)
+    if [(s['SN'], s['LN']) for s in sq] != list(zip(bam.names, bam.lengths)):
+      raise ValueError('the @SQ lines of the header text are not the BAM\'s reference list')
+    ctx = _native.Context(device)
+    try:
+      ctx.bq_begin(len(sq))
+      while True:
+        recs, nbytes, roff, n = bam.next_raw(chunk_bytes)
+        if n == 0:
+          break
+        ctx.bq_add_raw(recs, nbytes, roff, n)
+      return _results(ctx, sq)
+    finally:
+      ctx.close()
+  finally:
+    bam.close()
+
+
+def from_store(ctx, sq):
+  """(bq_data dict, counts) of the context's own god-aligner record store, no file in between."""
+  ctx.bq_begin(len(sq))
+  ctx.bq_add_store()
+  return _results(ctx, sq)
+
+
+def process_bam_parallel(bam_fname, pkl, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
+  """Write the per-contig (500, 100) uint64 matrices of `bam_fname` to `pkl` and return them (:38-54)."""
+  t0 = time.time()
+  bq_data, counts = count_bam(bam_fname, threads, device, chunk_bytes)
+  dt = max(time.time() - t0, 1e-9)
+  logger.debug('Processed {} records ({} r/s); {}'.format(counts and counts['seen'], (counts or {}).get('seen', 0) / dt,
+                                                          counts))
+  with open(pkl, 'wb') as fp:
+    pickle.dump(bq_data, fp)
+  return bq_data
