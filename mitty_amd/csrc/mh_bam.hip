@@ -298,12 +298,14 @@ struct StoreOff64 {
   __device__ void operator()(int64_t i, int64_t, int64_t excl) const { off[i] = base + excl; }
 };
 
-__device__ __forceinline__ uint8_t nt16(uint8_t c) {   // htslib seq_nt16_table: letters a..z (either case) from
-  // two nibble tables (selects, no branches or table loads), '=' 0, anything else 15
+__device__ __forceinline__ uint8_t nt16(uint8_t c) {   // htslib seq_nt16_table (stated from memory of hts.c, see
+  // DESIGN.md "Parity unpinned"): the IUPAC letters in either case from two nibble tables (selects, no branches or
+  // table loads; 'U' is 15, not T's 8), '=' 0, '0'..'3' 1, 2, 4, 8, anything else 15
   const uint32_t x = (uint32_t)(c | 0x20) - 'a';
-  const uint64_t lo = 0xfff3fcffb4ffd2e1ull, hi = 0xfaf978865full;
+  const uint64_t lo = 0xfff3fcffb4ffd2e1ull, hi = 0xfaf97f865full;
   const uint32_t v = (uint32_t)((x < 16 ? lo >> ((4 * x) & 63) : hi >> ((4 * (x - 16)) & 63)) & 15u);
-  return (uint8_t)(x < 26 ? v : c == '=' ? 0u : 15u);
+  const uint32_t dg = (uint32_t)c - '0';
+  return (uint8_t)(x < 26 ? v : c == '=' ? 0u : dg < 4 ? 1u << dg : 15u);
 }
 __device__ __forceinline__ uint8_t comp_atcgn(uint8_t c) {   // str.maketrans('ATCGN', 'TAGCN')
   return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
@@ -1316,6 +1318,8 @@ int32_t bam_partition(mh_ctx *ctx, const uint64_t *split, int32_t n_dest, uint64
   for (int32_t d = 0; d <= n_dest; d++) seg_off[d] = seg[d];
   MH_TRY(ensure(ctx, B.send, (size_t)seg[n_dest] + 64));
   B.send_bytes = seg[n_dest];
+  for (int32_t d = 0; d < n_dest; d++)   // an empty segment is its one record offset, 0 (no record's lane writes it)
+    if (seg_n[d] == 0) HIPCHK(ctx, hipMemsetAsync((uint8_t *)B.send.p + seg[d], 0, 8, st));
   if (n > 0) {
     HIPCHK(ctx, hipMemcpyAsync(B.part_seg.p, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
     int32_t *bad = (int32_t *)((char *)ctx->d_small.p + 76);

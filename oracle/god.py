@@ -10,11 +10,19 @@ Restates, in plain Python:
 The BAM bytes and the BAI are pinned by the specification only (no htslib / samtools in the image): parity
 unpinned beyond the record attributes.
 """
+import bisect
 import struct
 import zlib
 
 DNA_complement = str.maketrans('ATCGN', 'TAGCN')
-_NT16 = {c: i for i, c in enumerate('=ACMGRSVTWYHKDBN')}
+# htslib's seq_nt16_table (hts.c), stated from memory (no htslib in the image: parity unpinned, DESIGN.md): the IUPAC
+# letters in either case take their code, '=' is 0, '0'..'3' are A, C, G, T (1, 2, 4, 8), every other byte — 'U'
+# among them — is 15 (N)
+_NT16 = [15] * 256
+for _i, _c in enumerate('=ACMGRSVTWYHKDBN'):
+  _NT16[ord(_c)] = _NT16[ord(_c.lower())] = _i
+for _i, _c in enumerate('0123'):
+  _NT16[ord(_c)] = 1 << _i
 _CIGAR = {c: i for i, c in enumerate('MIDNSHP=X')}
 
 
@@ -92,11 +100,11 @@ def encode(r):
   """BAM record bytes (block_size included) for an attribute dict."""
   ops = _cigar_ops(r['cigarstring'])
   seq, qual = r['seq'], r['qual']
-  qn = r['qname'].encode() + b'\0'
+  qn = r['qname'].encode('latin-1') + b'\0'
   packed = bytearray()
   for i in range(0, len(seq), 2):
-    hi = _NT16.get(seq[i].upper(), 15)
-    lo = _NT16.get(seq[i + 1].upper(), 15) if i + 1 < len(seq) else 0
+    hi = _NT16[ord(seq[i])]
+    lo = _NT16[ord(seq[i + 1])] if i + 1 < len(seq) else 0
     packed.append(hi << 4 | lo)
   body = struct.pack('<iiBBHHHIiii', r['reference_id'], r['pos'], len(qn), r['mapq'], reg2bin(r['pos'], end_pos(r)),
                      len(ops), flag(r), len(seq), r.get('rnext', -1), r.get('pnext', -1), 0)
@@ -110,9 +118,10 @@ def sort_key(r):
 
 
 def god_records(fq1_bytes, fq2_bytes, ref_dict, max_templates=None):
-  """Attribute dicts of every record of a FASTQ (pair), in input order."""
-  l1 = fq1_bytes.decode().split('\n')
-  l2 = fq2_bytes.decode().split('\n') if fq2_bytes is not None else None
+  """Attribute dicts of every record of a FASTQ (pair), in input order.  Bytes map to characters one to one
+  (latin-1), so a sequence may hold any byte but the line feed."""
+  l1 = fq1_bytes.decode('latin-1').split('\n')
+  l2 = fq2_bytes.decode('latin-1').split('\n') if fq2_bytes is not None else None
   n = len(l1) // 4
   out = []
   for i in range(n):
@@ -167,11 +176,12 @@ def record_voffsets(data):
     starts.append((u, off, len(raw)))
     u += len(raw)
   stream = b''.join(raw for _, raw in blocks)
+  ustarts = [us for us, _, _ in starts]
 
   def voff(x):
-    for us, off, ln in starts:
-      if us <= x < us + ln:
-        return off << 16 | (x - us)
+    us, off, ln = starts[bisect.bisect_right(ustarts, x) - 1]   # (the last block starting at or before x)
+    if us <= x < us + ln:
+      return off << 16 | (x - us)
     # the end of the data: bgzf_tell after the last record points into the still-open last block unless that
     # block filled up (then flushed: the next block, i.e. the EOF marker, at offset 0)
     for us, off, ln in reversed(starts):

@@ -1421,9 +1421,11 @@ def _god_inputs(model, tmp_path):
 
 
 def _nt16_fold(seq):
-  """A sequence as a BAM record stores it (4-bit codes: case folded, unknown letters -> N)."""
-  codes = '=ACMGRSVTWYHKDBN'
-  return ''.join(c.upper() if c.upper() in codes else 'N' for c in seq)
+  """A sequence as a BAM record stores it (htslib's seq_nt16_table as oracle/god.py states it: IUPAC letters case
+  folded, '=' kept, '0'..'3' -> A, C, G, T, every other byte -> N)."""
+  codes = 'ACMGRSVTWYHKDBN'
+  return ''.join(c.upper() if c.upper() in codes else '=' if c == '=' else 'ACGT'[int(c)] if c in '0123' else 'N'
+                 for c in seq)
 
 
 @pytest.mark.parametrize('model', G.MODELS)
