@@ -378,9 +378,17 @@ int32_t mh_bam_bai_runs(mh_ctx *ctx, int64_t *n_runs, int64_t *runs, int64_t run
  *                      the caller's work on one chunk overlaps the inflate of the next.  One thread uses a handle at
  *                      a time.  mh_bamfile_header may be called whenever the open succeeded; mh_bamfile_error reads the
  *                      message that thread may be writing, so call it only after a call on the handle has returned an
- *                      error (the thread has been joined by then and none is started after a failure) */
+ *                      error (the thread has been joined by then and none is started after a failure)
+ *   mh_bamfile_open_gpu  the same reader with each batch of blocks inflated and CRC-checked on device `device` in one
+ *                      launch (mh_inflate.hip: a wave per block, the window in LDS) instead of on the threads: the
+ *                      compressed payloads go down through page-locked memory, the inflated bytes come back into the
+ *                      handle's buffer, and the header walk, the record checks, the chunks and every error text are
+ *                      the host path's.  The accept rule is zlib's.  The handle owns its stream and buffers (no mh_ctx),
+ *                      so its read-ahead thread never touches a context the caller is queueing work on.  Opt-in:
+ *                      --gpu-inflate of mq-plot, derr-plot, bam2illumina, gc-cov and bq */
 typedef struct mh_bamfile mh_bamfile;
 int32_t mh_bamfile_open(const char *path, int32_t threads, mh_bamfile **out);
+int32_t mh_bamfile_open_gpu(const char *path, int32_t device, int32_t threads, mh_bamfile **out);
 const char *mh_bamfile_error(const mh_bamfile *f);
 int32_t mh_bamfile_header(const mh_bamfile *f, const char **text, int64_t *text_len, int32_t *n_ref,
                           const char **names, const int64_t **lengths);
@@ -547,6 +555,13 @@ int32_t mh_bgzf_eof(char *out28);
 int32_t mh_bgzf_compress_device(mh_ctx *ctx, const void *d_in, int64_t len, void *d_out, int64_t cap,
                                 int64_t *used);
 int32_t mh_bgzf_compress_gpu(mh_ctx *ctx, const char *in, int64_t len, char *out, int64_t cap, int64_t *used);
+/* The other direction (mh_inflate.hip), and the known-answer hook of the reader's device inflate: a whole BGZF byte
+ * string in host memory -> its inflated bytes in out, with the reader's header walk and checks (CRC32 and ISIZE per
+ * member; a member of ISIZE 0, such as the EOF marker, inflates to nothing and is still checked).  MH_E_CAPACITY with
+ * *used = the bytes needed when cap is short; MH_E_ARG with *bad_offset = the file offset of the first bad block on
+ * any failure of the input.  No context: the call makes and frees its own stream and buffers on `device`. */
+int32_t mh_bgzf_inflate_gpu(int32_t device, const char *in, int64_t len, char *out, int64_t cap, int64_t *used,
+                            int64_t *bad_offset);
 int32_t mh_output_bgzf(mh_ctx *ctx, int32_t file, char *out, int64_t cap, int64_t *used);
 /* Known-answer hook of the device deflate (no reference counterpart: the compressed bytes are this library's own):
  * mh_bgzf_compress_gpu with the input staged `misalign` bytes (0..15) past a 16-byte boundary, so a test reaches the

@@ -28,7 +28,7 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_output_bgzf_range', 'mh_output_bgzf_pair', 'mh_output_bgzf_wait', 'mh_output_fetch_async',
            'mh_output_fetch_wait',
            'mh_vcf_open', 'mh_vcf_error', 'mh_vcf_close', 'mh_vcf_region', 'mh_vcf_copy', 'mh_vcf_filter',
-           'mh_bamfile_open', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
+           'mh_bamfile_open', 'mh_bamfile_open_gpu', 'mh_bgzf_inflate_gpu', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
            'mh_score_begin', 'mh_score_add_records', 'mh_score_add_store', 'mh_score_result', 'mh_score_reset',
            'mh_model_begin', 'mh_model_add_records', 'mh_model_add_store', 'mh_model_result', 'mh_model_reset',
            'mh_cov_begin', 'mh_cov_add_records', 'mh_cov_add_store', 'mh_cov_gc', 'mh_cov_result', 'mh_cov_reset',
@@ -154,6 +154,8 @@ def lib():
   _sig(L, 'mh_vcf_filter', [ctypes.c_char_p, ctypes.c_char_p, c_i32, c_vp, c_vp, c_vp, ctypes.c_char_p, c_i32, c_i32,
                             P_i64, P_i64, ctypes.c_char_p, c_i32])
   _sig(L, 'mh_bamfile_open', [ctypes.c_char_p, c_i32, ctypes.POINTER(c_vp)])
+  _sig(L, 'mh_bamfile_open_gpu', [ctypes.c_char_p, c_i32, c_i32, ctypes.POINTER(c_vp)])
+  _sig(L, 'mh_bgzf_inflate_gpu', [c_i32, c_vp, c_i64, c_vp, c_i64, P_i64, P_i64])
   _sig(L, 'mh_bamfile_error', [c_vp], ctypes.c_char_p)
   _sig(L, 'mh_bamfile_header', [c_vp, ctypes.POINTER(c_vp), P_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_vp),
                                 ctypes.POINTER(c_vp)])
@@ -289,13 +291,17 @@ class VcfFile:
 
 class BamFile:
   """Host BAM reader (mh_bamread.cpp): header fields, then chunks() of whole records.  `threads` sizes the inflate
-  pool."""
+  pool; with a `device` ordinal the BGZF blocks are inflated on that GPU instead (mh_bamfile_open_gpu: the same
+  records, chunks, checks and error texts)."""
 
-  def __init__(self, path, threads=2):
+  def __init__(self, path, threads=2, device=None):
     L = lib()
     self._L = L
     self._h = c_vp()
-    rc = L.mh_bamfile_open(path.encode(), int(threads), ctypes.byref(self._h))
+    if device is None:
+      rc = L.mh_bamfile_open(path.encode(), int(threads), ctypes.byref(self._h))
+    else:
+      rc = L.mh_bamfile_open_gpu(path.encode(), int(device), int(threads), ctypes.byref(self._h))
     if rc:
       msg = L.mh_bamfile_error(self._h).decode(errors='replace') if self._h else 'mh_bamfile_open failed'
       self.close()
@@ -430,6 +436,26 @@ def read_fasta(path, names=None):
   finally:
     if h:
       L.mh_fasta_close(h)
+
+
+def bgzf_inflate_gpu(data, device=0):
+  """The bytes a BGZF byte string inflates to, every member inflated and CRC-checked on the GPU (mh_bgzf_inflate_gpu).
+  A bad member raises ValueError; its file offset is the exception's bad_offset."""
+  n = len(data)
+  src = np.frombuffer(data, np.uint8) if n else np.zeros(1, np.uint8)
+  used, bad = c_i64(), c_i64()
+  rc = lib().mh_bgzf_inflate_gpu(int(device), _ptr(src), n, None, 0, ctypes.byref(used), ctypes.byref(bad))
+  out = np.empty(max(used.value, 1), np.uint8)
+  if rc in (MH_OK, MH_E_CAPACITY):
+    rc = lib().mh_bgzf_inflate_gpu(int(device), _ptr(src), n, _ptr(out), used.value, ctypes.byref(used),
+                                   ctypes.byref(bad))
+  if rc == MH_E_ARG:
+    e = ValueError('bad BGZF block at offset {}'.format(bad.value))
+    e.bad_offset = bad.value
+    raise e
+  if rc:
+    _raise(rc, 'mh_bgzf_inflate_gpu failed')
+  return out[:used.value].tobytes()
 
 
 def device_cache_trim():

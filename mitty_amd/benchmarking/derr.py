@@ -10,14 +10,14 @@ logger = logging.getLogger(__name__)
 
 
 def process_bam(bam_fname, max_v_len=200, max_d=200, strict=False, sample_name=None, processes=2, out_csv=None,
-                device=0):
+                device=0, gpu_inflate=False):
   """derr.process_bam (derr.py:19-46): d_err_mat u64[2 max_v_len + 2, 2 max_d + 1]; row max_v_len + v per variant
   size v a read carries (deletions negative), the last row for reads without variants."""
   if max_v_len < 51:
     logger.warning('Setting max_v_len to 51')
     max_v_len = 51
   _, d_err_mat, _ = score_bam(bam_fname, max_d=max_d, max_v_len=max_v_len, strict=strict, sample_name=sample_name,
-                              processes=processes, device=device)
+                              processes=processes, device=device, gpu_inflate=gpu_inflate)
   if out_csv is not None:
     logger.debug('Saving d_err matrix to {}'.format(out_csv))
     np.savetxt(out_csv, d_err_mat, delimiter=',', fmt='%d')

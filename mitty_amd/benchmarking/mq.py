@@ -10,10 +10,11 @@ from mitty_amd.benchmarking.score import score_bam
 logger = logging.getLogger(__name__)
 
 
-def process_bam(bam_fname, max_d=200, strict=False, sample_name=None, processes=2, out_csv=None, device=0):
+def process_bam(bam_fname, max_d=200, strict=False, sample_name=None, processes=2, out_csv=None, device=0,
+                gpu_inflate=False):
   """mq.process_bam (mq.py:20-43): mq_mat u64[100, 2 max_d + 1], mq_mat[mapq, d_err + max_d] = reads."""
   mq_mat, _, _ = score_bam(bam_fname, max_d=max_d, strict=strict, sample_name=sample_name, processes=processes,
-                           device=device)
+                           device=device, gpu_inflate=gpu_inflate)
   if out_csv is not None:
     logger.debug('Saving MQ matrix to {}'.format(out_csv))
     np.savetxt(out_csv, mq_mat, delimiter=',', fmt='%d')

@@ -11,12 +11,12 @@ CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
 
 
 def score_bam(bam_fname, max_d=200, max_v_len=200, strict=False, sample_name=None, processes=2, device=0,
-              chunk_bytes=CHUNK_BYTES):
+              chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """(mq_mat, d_err_mat, counts) of every record of `bam_fname` placed on a reference (mq.py:50-68, derr.py:53-76
   summed over the header's @SQ lines).  `processes` sizes the inflate pool; chunk k is scored on the device while the
-  reader inflates chunk k + 1."""
+  reader inflates chunk k + 1.  gpu_inflate: the BGZF blocks are inflated on `device` instead of on the pool."""
   t0 = time.time()
-  bam = _native.BamFile(bam_fname, threads=max(1, int(processes)))
+  bam = _native.BamFile(bam_fname, threads=max(1, int(processes)), device=device if gpu_inflate else None)
   try:
     ctx = _native.Context(device)
     try:

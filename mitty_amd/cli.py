@@ -2,7 +2,8 @@
 
 Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), mq-plot and derr-plot (GPU scoring, host
 BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; additive --device), gc-cov and bq (GPU
-depth track, block sums and histograms, host BAM reader; additive --device), filter-variants
+depth track, block sums and histograms, host BAM reader; additive --device), all five with the additive --gpu-inflate
+(the reader's BGZF blocks inflated on the --device GPU instead of on the host threads), filter-variants
 (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
 --rng {mitty,philox}, --corrupt-seed (fused Philox corruption); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
@@ -42,10 +43,12 @@ def filter_vcf(vcfin, sample, bed, vcfout):
 @click.option('-b', '--block-len', type=int, default=10000, help='Block size for GC/cov computation')
 @click.option('-t', '--threads', type=int, default=1, help='Threads to use')
 @click.option('--device', default=0, help='HIP device ordinal')
-def gc_cov(bam, fasta, pkl, block_len, threads, device):
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU (additive option)")
+def gc_cov(bam, fasta, pkl, block_len, threads, device, gpu_inflate):
   """Calculate GC content vs coverage from a BAM. Save in pickle file (reference cli.py:32-42)"""
   from mitty_amd.empirical import gc
-  gc.process_bam_parallel(bam, fasta, pkl, block_len=block_len, threads=threads, device=device)
+  gc.process_bam_parallel(bam, fasta, pkl, block_len=block_len, threads=threads, device=device,
+                          gpu_inflate=gpu_inflate)
 
 
 @cli.command('bq')
@@ -53,10 +56,11 @@ def gc_cov(bam, fasta, pkl, block_len, threads, device):
 @click.argument('pkl')
 @click.option('-t', '--threads', type=int, default=1, help='Threads to use')
 @click.option('--device', default=0, help='HIP device ordinal')
-def sample_bq(bam, pkl, threads, device):
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU (additive option)")
+def sample_bq(bam, pkl, threads, device, gpu_inflate):
   """BQ distribution from BAM (reference cli.py:45-51)"""
   from mitty_amd.empirical import bq
-  bq.process_bam_parallel(bam, pkl, threads=threads, device=device)
+  bq.process_bam_parallel(bam, pkl, threads=threads, device=device, gpu_inflate=gpu_inflate)
 
 
 @cli.command('bam2illumina', short_help='Create read model from BAM file')
@@ -69,13 +73,15 @@ def sample_bq(bam, pkl, threads, device):
 @click.option('--max-bp', type=int, default=300, help='Maximum length of read')
 @click.option('--max-tlen', type=int, default=1000, help='Maximum size of insert')
 @click.option('--device', default=0, help='HIP device ordinal')
-def bam2illumina(bam, pkl, desc, every, min_mq, threads, max_bp, max_tlen, device):
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU (additive option)")
+def bam2illumina(bam, pkl, desc, every, min_mq, threads, max_bp, max_tlen, device, gpu_inflate):
   """Process BAM file and create an empirical model of template length and base quality
   distribution. The model is saved to a Python pickle file usable by Mitty read generation programs
   (reference cli.py:54-68)."""
   from mitty_amd.empirical import bam2illumina as b2m
   b2m.process_bam_parallel(bam, pkl, model_description=desc, every=max(1, every), min_mq=min_mq,
-                           threads=threads, max_bq=94, max_bp=max_bp, max_tlen=max_tlen, device=device)
+                           threads=threads, max_bq=94, max_bp=max_bp, max_tlen=max_tlen, device=device,
+                           gpu_inflate=gpu_inflate)
 
 
 @cli.command('list-read-models')
@@ -208,10 +214,12 @@ def god_aligner(fasta, bam, sample_name, fastq1, fastq2, max_templates, threads,
 @click.option('--sample-name', help='If the FASTQ contains multiple samples, process reads from only this sample')
 @click.option('--threads', default=2)
 @click.option('--device', default=0, help='HIP device ordinal')
-def mq_plot(bam, csv, plot, max_d, strict_scoring, sample_name, threads, device):
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU (additive option)")
+def mq_plot(bam, csv, plot, max_d, strict_scoring, sample_name, threads, device, gpu_inflate):
   """Given a BAM from simulated reads, construct an MQ plot (reference cli.py:224-236)"""
   from mitty_amd.benchmarking import mq
-  mq_mat = mq.process_bam(bam, max_d, strict_scoring, sample_name, threads, csv, device=device)
+  mq_mat = mq.process_bam(bam, max_d, strict_scoring, sample_name, threads, csv, device=device,
+                          gpu_inflate=gpu_inflate)
   mq.plot_mq(mq_mat, plot)   # (logs and skips the figure when matplotlib is not installed; the CSV is written)
 
 
@@ -225,10 +233,12 @@ def mq_plot(bam, csv, plot, max_d, strict_scoring, sample_name, threads, device)
 @click.option('--sample-name', help='If the FASTQ contains multiple samples, process reads from only this sample')
 @click.option('--threads', default=2)
 @click.option('--device', default=0, help='HIP device ordinal')
-def derr_plot(bam, csv, plot, max_v, max_d, strict_scoring, sample_name, threads, device):
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU (additive option)")
+def derr_plot(bam, csv, plot, max_v, max_d, strict_scoring, sample_name, threads, device, gpu_inflate):
   """Given a BAM from simulated reads, show pattern of alignment errors (reference cli.py:239-252)"""
   from mitty_amd.benchmarking import derr
-  derr_mat = derr.process_bam(bam, max_v, max_d, strict_scoring, sample_name, threads, csv, device=device)
+  derr_mat = derr.process_bam(bam, max_v, max_d, strict_scoring, sample_name, threads, csv, device=device,
+                              gpu_inflate=gpu_inflate)
   derr.plot_derr(derr_mat, plot)
 
 

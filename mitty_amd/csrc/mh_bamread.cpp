@@ -3,7 +3,8 @@
 //
 //   file (mapped) -> BGZF block headers walked in order (BSIZE from the 'BC' extra field, ISIZE from the trailer, so
 //                    every block's place in the uncompressed stream is known before it is inflated)
-//                 -> raw inflate of a batch of blocks on `threads` threads, CRC32 and ISIZE checked per block
+//                 -> raw inflate of a batch of blocks on `threads` threads, CRC32 and ISIZE checked per block (or, for a
+//                    handle of mh_bamfile_open_gpu, the batch inflated and checked in one launch: mh_inflate.hip)
 //                 -> the BAM header (text, n_ref, names, lengths), then the record stream handed out in chunks cut at
 //                    record boundaries, with each chunk's record offsets; the chunk after the one handed out is
 //                    inflated and cut by a thread of the handle meanwhile (read-ahead, a second buffer)
@@ -25,6 +26,8 @@
 
 #include "../../include/mitty_hip.h"
 #include "mh_bamread.h"
+#define MH_INFLATE_OPTIONAL   // (this file links without mh_inflate.hip too: see mh_inflate.h)
+#include "mh_inflate.h"
 
 namespace mh {
 
@@ -60,6 +63,7 @@ struct mh_bamfile {
   const uint8_t *map = nullptr;
   int64_t fsize = 0, fpos = 0;   // the mapped file and the next BGZF block's offset
   int threads = 1;
+  mh::Inflater *gpu = nullptr;   // mh_bamfile_open_gpu: fill() hands its batch to the device instead of the threads
   // Uncompressed bytes not handed out yet, [head, buf.size()), and the chunk cut from them.  Two sides: while the caller
   // works on the chunk of one, a thread of the handle inflates and cuts the next chunk in the other (read-ahead).
   struct Side {
@@ -93,6 +97,54 @@ struct Blk {
   uint32_t crc, isize;
 };
 
+// The BGZF block header at file offset o (p: its bytes, left: the bytes from there to the end): the payload's place,
+// CRC32 and ISIZE into b, the block's size into *bsize.  False with the message in *why.
+bool walk_block(const uint8_t *p, int64_t o, int64_t left, Blk *b, int64_t *bsize_out, std::string *why) {
+  auto bad = [&](const char *m) {
+    *why = m + std::to_string(o);
+    return false;
+  };
+  if (left < 18) return bad("truncated BGZF block header at offset ");
+  if (p[0] != 31 || p[1] != 139 || p[2] != 8 || !(p[3] & 4)) return bad("not a BGZF block at offset ");
+  const int64_t xlen = le16(p + 10);
+  if (12 + xlen > left) return bad("truncated BGZF extra field at offset ");
+  int64_t bsize = -1;
+  for (int64_t x = 12; x + 4 <= 12 + xlen;) {
+    const int64_t slen = le16(p + x + 2);
+    if (x + 4 + slen > 12 + xlen) break;
+    if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2) bsize = (int64_t)le16(p + x + 4) + 1;
+    x += 4 + slen;
+  }
+  if (bsize < 0) return bad("BGZF block without a BC field at offset ");
+  if (bsize < 12 + xlen + 8) return bad("BGZF block size too small at offset ");
+  if (bsize > left) return bad("truncated BGZF block at offset ");
+  b->cpos = o + 12 + xlen;
+  b->clen = bsize - 12 - xlen - 8;
+  b->crc = le32(p + bsize - 8);
+  b->isize = le32(p + bsize - 4);
+  if (b->isize > 65536) return bad("BGZF block ISIZE over 64 KiB at offset ");
+  *bsize_out = bsize;
+  return true;
+}
+
+std::string inflate_message(int64_t cpos) {
+  return "BGZF block fails to inflate or its CRC32 / ISIZE differs (payload at offset " + std::to_string(cpos) + ")";
+}
+
+// blks inflated on the device into out (each at its dst - dst0).  *bad: the lowest failing payload offset, or -1.
+int32_t inflate_gpu(mh::Inflater *g, const uint8_t *map, const std::vector<Blk> &blks, int64_t dst0, uint8_t *out,
+                    int64_t out_bytes, int threads, int64_t *bad, std::string *err) {
+  std::vector<mh::InflateMember> m(blks.size());
+  for (size_t k = 0; k < blks.size(); k++)
+    m[k] = mh::InflateMember{blks[k].cpos, blks[k].dst - dst0, (uint32_t)blks[k].clen, blks[k].isize, blks[k].crc, 0};
+  *bad = -1;
+  const int32_t rc = mh::inflater_run(g, map, m.data(), m.size(), out, out_bytes, threads, err);
+  if (rc != MH_OK) return rc;
+  for (size_t k = 0; k < m.size(); k++)
+    if (m[k].status != 0 && (*bad < 0 || blks[k].cpos < *bad)) *bad = blks[k].cpos;
+  return MH_OK;
+}
+
 // Inflates BGZF blocks from fpos until at least `want` more bytes are in buf or the file ends.
 int32_t fill(mh_bamfile *f, mh_bamfile::Side &s, int64_t want) {
   std::vector<Blk> blks;
@@ -100,31 +152,14 @@ int32_t fill(mh_bamfile *f, mh_bamfile::Side &s, int64_t want) {
     s.buf.erase(s.buf.begin(), s.buf.begin() + s.head);
     s.head = 0;
   }
-  int64_t dst = (int64_t)s.buf.size(), got = 0;
+  const int64_t dst0 = (int64_t)s.buf.size();
+  int64_t dst = dst0, got = 0;
   while (got < want && f->fpos < f->fsize) {
-    const int64_t o = f->fpos, left = f->fsize - o;
-    const uint8_t *p = f->map + o;
-    if (left < 18) return fail(f, "truncated BGZF block header at offset " + std::to_string(o));
-    if (p[0] != 31 || p[1] != 139 || p[2] != 8 || !(p[3] & 4))
-      return fail(f, "not a BGZF block at offset " + std::to_string(o));
-    const int64_t xlen = le16(p + 10);
-    if (12 + xlen > left) return fail(f, "truncated BGZF extra field at offset " + std::to_string(o));
-    int64_t bsize = -1;
-    for (int64_t x = 12; x + 4 <= 12 + xlen;) {
-      const int64_t slen = le16(p + x + 2);
-      if (x + 4 + slen > 12 + xlen) break;
-      if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2) bsize = (int64_t)le16(p + x + 4) + 1;
-      x += 4 + slen;
-    }
-    if (bsize < 0) return fail(f, "BGZF block without a BC field at offset " + std::to_string(o));
-    if (bsize < 12 + xlen + 8) return fail(f, "BGZF block size too small at offset " + std::to_string(o));
-    if (bsize > left) return fail(f, "truncated BGZF block at offset " + std::to_string(o));
+    const int64_t o = f->fpos;
     Blk b;
-    b.cpos = o + 12 + xlen;
-    b.clen = bsize - 12 - xlen - 8;
-    b.crc = le32(p + bsize - 8);
-    b.isize = le32(p + bsize - 4);
-    if (b.isize > 65536) return fail(f, "BGZF block ISIZE over 64 KiB at offset " + std::to_string(o));
+    int64_t bsize = 0;
+    std::string why;
+    if (!walk_block(f->map + o, o, f->fsize - o, &b, &bsize, &why)) return fail(f, why);
     b.dst = dst;
     dst += b.isize;
     got += b.isize;
@@ -133,6 +168,19 @@ int32_t fill(mh_bamfile *f, mh_bamfile::Side &s, int64_t want) {
   }
   if (blks.empty()) return MH_OK;
   s.buf.resize((size_t)dst);
+  if (f->gpu) {
+    int64_t bad = -1;
+    std::string err;
+    const int32_t rc =
+        inflate_gpu(f->gpu, f->map, blks, dst0, s.buf.data() + dst0, dst - dst0, f->threads, &bad, &err);
+    if (rc != MH_OK) {
+      f->err = err;
+      f->failed = true;
+      return rc;
+    }
+    if (bad >= 0) return fail(f, inflate_message(bad));
+    return MH_OK;
+  }
   std::atomic<size_t> next{0};
   std::atomic<int64_t> bad{-1};
   auto work = [&]() {
@@ -165,9 +213,7 @@ int32_t fill(mh_bamfile *f, mh_bamfile::Side &s, int64_t want) {
   for (int t = 1; t < nt; t++) pool.emplace_back(work);
   work();
   for (auto &t : pool) t.join();
-  if (bad.load() >= 0)
-    return fail(f, "BGZF block fails to inflate or its CRC32 / ISIZE differs (payload at offset " +
-                       std::to_string(bad.load()) + ")");
+  if (bad.load() >= 0) return fail(f, inflate_message(bad.load()));
   return MH_OK;
 }
 
@@ -254,12 +300,20 @@ int32_t cut_chunk(mh_bamfile *f, mh_bamfile::Side &s, int64_t max_bytes) {
 
 extern "C" {
 
-int32_t mh_bamfile_open(const char *path, int32_t threads, mh_bamfile **out) {
+static int32_t bamfile_open(const char *path, int32_t device, int32_t threads, mh_bamfile **out) {
   if (!path || !out) return MH_E_ARG;
   *out = nullptr;
   mh_bamfile *f = new mh_bamfile();
   *out = f;
   f->threads = std::max(1, std::min(threads, 256));
+  if (device >= 0) {
+    if (!mh::inflater_create) return fail(f, "this build of the reader has no device inflater");
+    const int32_t rc = mh::inflater_create(device, &f->gpu, &f->err);
+    if (rc != MH_OK) {
+      f->failed = true;
+      return rc;
+    }
+  }
   f->fd = open(path, O_RDONLY);
   if (f->fd < 0) return fail(f, std::string("cannot open ") + path);
   struct stat st;
@@ -272,6 +326,61 @@ int32_t mh_bamfile_open(const char *path, int32_t threads, mh_bamfile **out) {
   const int32_t rc = read_header(f);
   f->opened = rc == MH_OK;
   return rc;
+}
+
+int32_t mh_bamfile_open(const char *path, int32_t threads, mh_bamfile **out) {
+  return bamfile_open(path, -1, threads, out);
+}
+
+int32_t mh_bamfile_open_gpu(const char *path, int32_t device, int32_t threads, mh_bamfile **out) {
+  if (device < 0) return MH_E_ARG;
+  return bamfile_open(path, device, threads, out);
+}
+
+int32_t mh_bgzf_inflate_gpu(int32_t device, const char *in, int64_t len, char *out, int64_t cap, int64_t *used,
+                            int64_t *bad_offset) {
+  if (used) *used = 0;
+  if (bad_offset) *bad_offset = -1;
+  if (device < 0 || len < 0 || cap < 0 || (len > 0 && !in) || (cap > 0 && !out) || !used) return MH_E_ARG;
+  const uint8_t *p = (const uint8_t *)in;
+  std::vector<Blk> blks;
+  std::vector<int64_t> at;   // the blocks' offsets
+  int64_t dst = 0;
+  for (int64_t o = 0; o < len;) {
+    Blk b;
+    int64_t bsize = 0;
+    std::string why;
+    if (!walk_block(p + o, o, len - o, &b, &bsize, &why)) {
+      if (bad_offset) *bad_offset = o;
+      return MH_E_ARG;
+    }
+    b.dst = dst;
+    dst += b.isize;
+    blks.push_back(b);
+    at.push_back(o);
+    o += bsize;
+  }
+  *used = dst;
+  if (dst > cap) return MH_E_CAPACITY;
+  if (blks.empty()) return MH_OK;
+  mh::Inflater *g = nullptr;
+  std::string err;
+  if (!mh::inflater_create) return MH_E_STATE;
+  int32_t rc = mh::inflater_create(device, &g, &err);
+  if (rc != MH_OK) return rc;
+  uint8_t none = 0;
+  int64_t bad = -1;
+  rc = inflate_gpu(g, p, blks, 0, cap > 0 ? (uint8_t *)out : &none, dst, 4, &bad, &err);
+  mh::inflater_destroy(g);
+  if (rc != MH_OK) return rc;
+  if (bad >= 0) {
+    int64_t o = 0;   // the block whose payload starts at `bad`
+    for (size_t k = 0; k < blks.size(); k++)
+      if (blks[k].cpos == bad) o = at[k];
+    if (bad_offset) *bad_offset = o;
+    return MH_E_ARG;
+  }
+  return MH_OK;
 }
 
 const char *mh_bamfile_error(const mh_bamfile *f) { return f ? f->err.c_str() : "null handle"; }
@@ -324,6 +433,7 @@ int32_t mh_bamfile_close(mh_bamfile *f) {
   if (f->ahead.joinable()) f->ahead.join();
   if (f->map) munmap(const_cast<uint8_t *>(f->map), (size_t)f->fsize);
   if (f->fd >= 0) close(f->fd);
+  if (f->gpu) mh::inflater_destroy(f->gpu);
   delete f;
   return MH_OK;
 }

@@ -16,10 +16,10 @@ CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
 
 
 def count_bam(bam_fname, every=1, min_mq=0, threads=4, max_bq=94, max_bp=300, max_tlen=1000, device=0,
-              chunk_bytes=CHUNK_BYTES):
+              chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """(bq_mat, tlen_mat, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk
-  k + 1.  `threads` sizes the inflate pool."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)))
+  k + 1.  `threads` sizes the inflate pool; gpu_inflate: the BGZF blocks are inflated on `device` instead."""
+  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
   try:
     ctx = _native.Context(device)
     try:
@@ -59,10 +59,11 @@ def model_from_counts(bq_mat, tlen_mat, r_cnt, min_rlen, max_rlen, model_descrip
 
 
 def process_bam_parallel(bam_fname, pkl, model_description='Test model', every=1, min_mq=0, threads=4, max_bq=94,
-                         max_bp=300, max_tlen=1000, device=0, chunk_bytes=CHUNK_BYTES):
+                         max_bp=300, max_tlen=1000, device=0, chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """Write the read model of `bam_fname` to `pkl` (a path ending in .npz: the pickle-free form) and return it."""
   t0 = time.time()
-  bq_mat, tlen_mat, counts = count_bam(bam_fname, every, min_mq, threads, max_bq, max_bp, max_tlen, device, chunk_bytes)
+  bq_mat, tlen_mat, counts = count_bam(bam_fname, every, min_mq, threads, max_bq, max_bp, max_tlen, device, chunk_bytes,
+                                       gpu_inflate)
   dt = max(time.time() - t0, 1e-9)
   logger.debug('Processed {} templates ({} t/s); {}'.format(counts['used'], counts['used'] / dt, counts))
   model = model_from_counts(bq_mat, tlen_mat, counts['used'], counts['min_rlen'], counts['max_rlen'],

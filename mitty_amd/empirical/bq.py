@@ -22,9 +22,10 @@ def _results(ctx, sq):
   return bq_data, counts
 
 
-def count_bam(bam_fname, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
-  """(bq_data dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)))
+def count_bam(bam_fname, threads=4, device=0, chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
+  """(bq_data dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1.
+  gpu_inflate: the BGZF blocks are inflated on `device` instead of on the `threads` pool."""
+  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
   try:
     sq = seq_info(bam.text, bam.names, bam.lengths)
     if [(s['SN'], s['LN']) for s in sq] != list(zip(bam.names, bam.lengths)):
@@ -51,10 +52,10 @@ def from_store(ctx, sq):
   return _results(ctx, sq)
 
 
-def process_bam_parallel(bam_fname, pkl, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
+def process_bam_parallel(bam_fname, pkl, threads=4, device=0, chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """Write the per-contig (500, 100) uint64 matrices of `bam_fname` to `pkl` and return them (:38-54)."""
   t0 = time.time()
-  bq_data, counts = count_bam(bam_fname, threads, device, chunk_bytes)
+  bq_data, counts = count_bam(bam_fname, threads, device, chunk_bytes, gpu_inflate)
   dt = max(time.time() - t0, 1e-9)
   logger.debug('Processed {} records ({} r/s); {}'.format(counts and counts['seen'], (counts or {}).get('seen', 0) / dt,
                                                           counts))

@@ -81,9 +81,11 @@ def _results(ctx, sq, block_len):
   return gc_cov, counts
 
 
-def count_bam(bam_fname, fasta_fname, block_len=10000, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
-  """(gc_cov dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)))
+def count_bam(bam_fname, fasta_fname, block_len=10000, threads=4, device=0, chunk_bytes=CHUNK_BYTES,
+              gpu_inflate=False):
+  """(gc_cov dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1.
+  gpu_inflate: the BGZF blocks are inflated on `device` instead of on the `threads` pool."""
+  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
   try:
     sq = seq_info(bam.text, bam.names, bam.lengths)
     if [(s['SN'], s['LN']) for s in sq] != list(zip(bam.names, bam.lengths)):
@@ -119,10 +121,11 @@ def from_store(ctx, sq, seqs, block_len=10000, contig_id=SCRATCH_CONTIG_ID):
   return _results(ctx, sq, block_len)
 
 
-def process_bam_parallel(bam_fname, fasta_fname, pkl, block_len=10000, threads=4, device=0, chunk_bytes=CHUNK_BYTES):
+def process_bam_parallel(bam_fname, fasta_fname, pkl, block_len=10000, threads=4, device=0, chunk_bytes=CHUNK_BYTES,
+                         gpu_inflate=False):
   """Write the GC / coverage arrays of `bam_fname` to `pkl` and return them (:62-78)."""
   t0 = time.time()
-  gc_cov, counts = count_bam(bam_fname, fasta_fname, block_len, threads, device, chunk_bytes)
+  gc_cov, counts = count_bam(bam_fname, fasta_fname, block_len, threads, device, chunk_bytes, gpu_inflate)
   dt = max(time.time() - t0, 1e-9)
   logger.debug('Processed {} records ({} r/s); {}'.format(counts and counts['seen'], (counts or {}).get('seen', 0) / dt,
                                                           counts))
