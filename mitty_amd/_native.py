@@ -515,6 +515,15 @@ def _raise(rc, msg):
   raise NativeError('libmitty_hip error {}: {}'.format(rc, msg))
 
 
+def _model_counts(cnt):
+  """The counts dict of mh_model_result / mh_bq_result; min_rlen None when no record was used."""
+  d = dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_every', 'skipped_flag', 'min_rlen',
+                'max_rlen'), (int(x) for x in cnt)))
+  if d['min_rlen'] == MODEL_NO_RLEN:
+    d['min_rlen'] = None
+  return d
+
+
 def read_model_params(mean_rlen, coverage):
   p, passes = c_dbl(), c_i64()
   rc = lib().mh_read_model_params(int(mean_rlen), float(coverage), ctypes.byref(p), ctypes.byref(passes))
@@ -1005,6 +1014,15 @@ class Context:
   def bam_reset(self):
     self._chk(self._L.mh_bam_reset(self._h))
 
+  # ---- the record sessions: what their add calls share ----
+  def _add_raw(self, add, recs_addr, nbytes, roff_addr, n):
+    self._chk(add(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+
+  def _add_records(self, add, recs, roff):
+    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
+    o = np.ascontiguousarray(roff, dtype=np.int64)
+    self._chk(add(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+
   # ---- alignment scoring (mq-plot / derr-plot) ----
   def score_begin(self, names, max_d=200, max_v_len=200, strict=False, sample_prefix=None):
     """A new scoring session.  names: the BAM header's reference names (list, or the NUL-separated blob)."""
@@ -1016,13 +1034,11 @@ class Context:
 
   def score_add_raw(self, recs_addr, nbytes, roff_addr, n):
     """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by score_result."""
-    self._chk(self._L.mh_score_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+    self._add_raw(self._L.mh_score_add_records, recs_addr, nbytes, roff_addr, n)
 
   def score_add_records(self, recs, roff):
     """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
-    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
-    o = np.ascontiguousarray(roff, dtype=np.int64)
-    self._chk(self._L.mh_score_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+    self._add_records(self._L.mh_score_add_records, recs, roff)
 
   def score_add_store(self):
     """Score the context's own BAM record store (bam_add_fastq / bam_add_output) in HBM."""
@@ -1049,13 +1065,11 @@ class Context:
 
   def model_add_raw(self, recs_addr, nbytes, roff_addr, n):
     """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by model_result."""
-    self._chk(self._L.mh_model_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+    self._add_raw(self._L.mh_model_add_records, recs_addr, nbytes, roff_addr, n)
 
   def model_add_records(self, recs, roff):
     """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
-    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
-    o = np.ascontiguousarray(roff, dtype=np.int64)
-    self._chk(self._L.mh_model_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+    self._add_records(self._L.mh_model_add_records, recs, roff)
 
   def model_add_store(self):
     """The context's own BAM record store (bam_add_fastq / bam_add_output) through the session, in HBM."""
@@ -1069,11 +1083,7 @@ class Context:
     tl = np.zeros(max_tlen, np.uint64)
     cnt = np.zeros(8, np.int64)
     self._chk(self._L.mh_model_result(self._h, _ptr(bq), _ptr(tl), _ptr(cnt)))
-    d = dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_every', 'skipped_flag', 'min_rlen',
-                  'max_rlen'), (int(x) for x in cnt)))
-    if d['min_rlen'] == MODEL_NO_RLEN:
-      d['min_rlen'] = None
-    return bq, tl, d
+    return bq, tl, _model_counts(cnt)
 
   def model_reset(self):
     self._chk(self._L.mh_model_reset(self._h))
@@ -1089,13 +1099,11 @@ class Context:
 
   def cov_add_raw(self, recs_addr, nbytes, roff_addr, n):
     """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by cov_result."""
-    self._chk(self._L.mh_cov_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+    self._add_raw(self._L.mh_cov_add_records, recs_addr, nbytes, roff_addr, n)
 
   def cov_add_records(self, recs, roff):
     """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
-    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
-    o = np.ascontiguousarray(roff, dtype=np.int64)
-    self._chk(self._L.mh_cov_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+    self._add_records(self._L.mh_cov_add_records, recs, roff)
 
   def cov_add_store(self):
     """The context's own BAM record store (bam_add_fastq / bam_add_output) through the session, in HBM."""
@@ -1136,12 +1144,10 @@ class Context:
     self._chk(self._L.mh_bq_begin(self._h, int(n_refs)))
 
   def bq_add_raw(self, recs_addr, nbytes, roff_addr, n):
-    self._chk(self._L.mh_bq_add_records(self._h, c_vp(recs_addr), int(nbytes), c_vp(roff_addr), int(n)))
+    self._add_raw(self._L.mh_bq_add_records, recs_addr, nbytes, roff_addr, n)
 
   def bq_add_records(self, recs, roff):
-    a = np.frombuffer(recs, np.uint8) if len(recs) else np.zeros(1, np.uint8)
-    o = np.ascontiguousarray(roff, dtype=np.int64)
-    self._chk(self._L.mh_bq_add_records(self._h, _ptr(a), len(recs), _ptr(o), len(o) - 1))
+    self._add_records(self._L.mh_bq_add_records, recs, roff)
 
   def bq_add_store(self):
     self._chk(self._L.mh_bq_add_store(self._h))
@@ -1151,11 +1157,7 @@ class Context:
     mat = np.zeros((BQ_MAX_BP, BQ_MAX_BQ), np.uint64)
     cnt = np.zeros(8, np.int64)
     self._chk(self._L.mh_bq_result(self._h, int(ref_index), _ptr(mat), _ptr(cnt)))
-    d = dict(zip(('seen', 'used', 'skipped_unplaced', 'skipped_ref', 'skipped_every', 'skipped_flag', 'min_rlen',
-                  'max_rlen'), (int(x) for x in cnt)))
-    if d['min_rlen'] == MODEL_NO_RLEN:
-      d['min_rlen'] = None
-    return mat, d
+    return mat, _model_counts(cnt)
 
   def bq_reset(self):
     self._chk(self._L.mh_bq_reset(self._h))

@@ -3,11 +3,10 @@
 import logging
 import time
 
-from mitty_amd import _native
+from mitty_amd.lib import bamsession
+from mitty_amd.lib.bamsession import CHUNK_BYTES
 
 logger = logging.getLogger(__name__)
-
-CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
 
 
 def score_bam(bam_fname, max_d=200, max_v_len=200, strict=False, sample_name=None, processes=2, device=0,
@@ -16,21 +15,10 @@ def score_bam(bam_fname, max_d=200, max_v_len=200, strict=False, sample_name=Non
   summed over the header's @SQ lines).  `processes` sizes the inflate pool; chunk k is scored on the device while the
   reader inflates chunk k + 1.  gpu_inflate: the BGZF blocks are inflated on `device` instead of on the pool."""
   t0 = time.time()
-  bam = _native.BamFile(bam_fname, threads=max(1, int(processes)), device=device if gpu_inflate else None)
-  try:
-    ctx = _native.Context(device)
-    try:
-      ctx.score_begin(bam.names_blob, max_d, max_v_len, strict, sample_name)
-      while True:
-        recs, nbytes, roff, n = bam.next_raw(chunk_bytes)
-        if n == 0:
-          break
-        ctx.score_add_raw(recs, nbytes, roff, n)
-      mq_mat, d_err_mat, counts = ctx.score_result()
-    finally:
-      ctx.close()
-  finally:
-    bam.close()
+  with bamsession.opened(bam_fname, processes, device, gpu_inflate) as (bam, ctx, _):
+    ctx.score_begin(bam.names_blob, max_d, max_v_len, strict, sample_name)
+    bamsession.feed(bam, ctx.score_add_raw, chunk_bytes)
+    mq_mat, d_err_mat, counts = ctx.score_result()
   dt = max(time.time() - t0, 1e-9)
   logger.debug('{} records scored in {:0.2f}s ({:0.2f} records/sec); {}'.format(counts['scored'], dt,
                                                                                  counts['scored'] / dt, counts))

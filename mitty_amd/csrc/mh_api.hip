@@ -1831,6 +1831,12 @@ int32_t mh_bam_write(mh_ctx *ctx, const char *bam_path, const char *header_text,
   return MH_OK;
 }
 
+// the arguments of a session's add_records
+static int32_t recs_args(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  return MH_OK;
+}
+
 // ---- alignment scoring (mh_score.hip) ---------------------------------------------------------------------------
 int32_t mh_score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_d, int32_t max_v_len,
                        int32_t strict, const char *sample_prefix) {
@@ -1840,7 +1846,7 @@ int32_t mh_score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t m
 
 int32_t mh_score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   CTX_GUARD(ctx);
-  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  MH_TRY(recs_args(ctx, recs, len, roff, n));
   return score_add_records(ctx, recs, len, roff, n);
 }
 
@@ -1868,7 +1874,7 @@ int32_t mh_model_begin(mh_ctx *ctx, int32_t n_refs, int32_t every, int32_t min_m
 
 int32_t mh_model_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   CTX_GUARD(ctx);
-  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  MH_TRY(recs_args(ctx, recs, len, roff, n));
   return model_add_records(ctx, ctx->model, recs, len, roff, n);
 }
 
@@ -1895,7 +1901,7 @@ int32_t mh_bq_begin(mh_ctx *ctx, int32_t n_refs) {
 
 int32_t mh_bq_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   CTX_GUARD(ctx);
-  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  MH_TRY(recs_args(ctx, recs, len, roff, n));
   return model_add_records(ctx, ctx->bq, recs, len, roff, n);
 }
 
@@ -1923,7 +1929,7 @@ int32_t mh_cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_
 
 int32_t mh_cov_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   CTX_GUARD(ctx);
-  if (n < 0 || len < 0 || (n > 0 && (!recs || !roff))) return arg_fail(ctx, MH_E_ARG, "null argument");
+  MH_TRY(recs_args(ctx, recs, len, roff, n));
   return cov_add_records(ctx, recs, len, roff, n);
 }
 

@@ -1,5 +1,5 @@
 // mh_bamread.h — the structural check every BAM record passes on the host before it is handed out by the reader
-// (mh_bamread.cpp) or uploaded for scoring (mh_score.hip).  Plain C++ (no HIP).
+// (mh_bamread.cpp) or uploaded to a record session (mh_recs.hip).  Plain C++ (no HIP).
 #pragma once
 
 #include <cstdint>

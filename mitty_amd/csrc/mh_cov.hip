@@ -33,6 +33,11 @@
 #include "mh_scan.h"
 
 namespace mh {
+
+const RecTexts COV_TEXTS = {
+    "gc-cov", "call mh_cov_begin first", "the record store has spilled to the host (mh_bam_set_capacity): use its BAM file",
+    {"", "fields do not fit the record", "tid outside the header's references", "pos outside its reference"}};
+
 namespace {
 
 constexpr int CV_REF = CovState::N_REF;
@@ -58,21 +63,16 @@ struct CovArgs {
   CovDesc *desc;
 };
 
-__device__ __forceinline__ uint32_t cv16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-__device__ __forceinline__ uint32_t cv32(const uint8_t *p) {
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
 __global__ void __launch_bounds__(256) k_cov_head(CovArgs a) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < a.n; t += (int64_t)gridDim.x * 256) {
-    const int64_t s = a.roff[t], e = a.roff[t + 1], size = e - s;
+    int64_t s, size;
     CovDesc d{0, 0, -1, CK_NONE};
     int32_t fail = 0;
-    if (size < 36 || s < 0 || e > a.avail) {
+    if (!rec_span(a.roff, t, a.avail, &s, &size)) {
       fail = CE_STRUCT;
     } else {
       const uint8_t *p = a.recs + s;
-      const int32_t tid = (int32_t)cv32(p + 4), flag = (int32_t)cv16(p + 18);
+      const int32_t tid = (int32_t)le32(p + 4), flag = (int32_t)le16(p + 18);
       if (tid < 0) {
         d.kind = CK_UNPLACED;   // pileup(region=SN:..) never yields these
       } else if (tid >= a.n_refs) {
@@ -82,16 +82,16 @@ __global__ void __launch_bounds__(256) k_cov_head(CovArgs a) {
       } else if (flag & CV_FLAG_MASK) {
         d.kind = CK_FLAG;
       } else {
-        const int64_t n_cig = cv16(p + 16), c0 = 36 + (int64_t)p[12];
+        const int64_t n_cig = le16(p + 16), c0 = 36 + (int64_t)p[12];
         if (c0 + 4 * n_cig > size) {
           fail = CE_STRUCT;
         } else {
           int64_t span = 0;
           for (int64_t i = 0; i < n_cig; i++) {
-            const uint32_t v = cv32(p + c0 + 4 * i), op = v & 15u;
+            const uint32_t v = le32(p + c0 + 4 * i), op = v & 15u;
             if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += (int64_t)(v >> 4);   // M D N = X
           }
-          const int64_t pos = (int64_t)(int32_t)cv32(p + 8);
+          const int64_t pos = (int64_t)(int32_t)le32(p + 8);
           if (span == 0) {
             d.kind = CK_NOSPAN;
           } else if (pos < 0 || pos >= a.ln[tid]) {
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) k_cov_head(CovArgs a) {
         }
       }
     }
-    if (fail) atomicMin(a.err, ((unsigned long long)(a.base_rec + t) << 4) | (unsigned long long)fail);
+    if (fail) rec_fail(a.err, a.base_rec + t, fail);
     a.desc[t] = d;
   }
 }
@@ -270,28 +270,27 @@ CovBlk cov_blk(const CovState &S) {
           (long long *)(p + 24 * n), (uint32_t *)(p + 32 * n), (uint32_t *)(p + 36 * n)};
 }
 
-int32_t cov_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail) {
+int32_t cov_launch(mh_ctx *ctx, const RecChunk &c) {
   CovState &S = ctx->cov;
   hipStream_t st = ctx->stream;
-  MH_TRY(ensure(ctx, S.desc, sizeof(CovDesc) * (size_t)n));
+  MH_TRY(ensure(ctx, S.desc, sizeof(CovDesc) * (size_t)c.n));
   const CovBlk b = cov_blk(S);
   const int64_t *tab = (const int64_t *)S.tab.p;
-  CovArgs a{recs, roff, n, avail, S.base_rec, S.block_len, S.n_refs, S.n_vis, tab, tab + CV_REF, tab + 2 * CV_REF + 1,
-            (int32_t *)S.track.p, b.span, b.minpos, b.maxend, (unsigned long long *)S.cnt.p,
-            (unsigned long long *)S.err.p, (CovDesc *)S.desc.p};
-  const unsigned grid = grid_for(n, 256, 8 * (int64_t)ctx->max_cu);
+  CovArgs a{c.recs, c.roff, c.n, c.avail, c.base_rec, S.block_len, S.n_refs, S.n_vis, tab, tab + CV_REF,
+            tab + 2 * CV_REF + 1, (int32_t *)S.track.p, b.span, b.minpos, b.maxend, (unsigned long long *)S.cnt.p,
+            (unsigned long long *)S.ses.err.p, (CovDesc *)S.desc.p};
+  const unsigned grid = grid_for(c.n, 256, 8 * (int64_t)ctx->max_cu);
   hipLaunchKernelGGL(k_cov_head, dim3(grid), dim3(256), 0, st, a);
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_cov_apply, dim3(grid), dim3(256), 0, st, a);
   HIPCHK(ctx, hipGetLastError());
-  S.base_rec += n;
   S.scanned = false;
   return MH_OK;
 }
 
 // checked before anything of the call is staged or queued
 int32_t cov_room(mh_ctx *ctx, int64_t n) {
-  if (ctx->cov.base_rec + n >= ((int64_t)1 << 31))
+  if (ctx->cov.ses.base_rec + n >= ((int64_t)1 << 31))
     return arg_fail(ctx, MH_E_CAPACITY, "gc-cov: 2^31 records or more in one session (the depth track is 32-bit)");
   return MH_OK;
 }
@@ -299,15 +298,13 @@ int32_t cov_room(mh_ctx *ctx, int64_t n) {
 int32_t cov_clear(mh_ctx *ctx) {
   CovState &S = ctx->cov;
   hipStream_t st = ctx->stream;
-  MH_TRY(stage_init(ctx, S.stage));
+  MH_TRY(session_clear(ctx, S.ses));
   const size_t n = (size_t)std::max<int64_t>(S.n_blk, 1);
   HIPCHK(ctx, hipMemsetAsync(S.track.p, 0, 4 * (size_t)std::max<int64_t>(S.n_cells, 1), st));
   HIPCHK(ctx, hipMemsetAsync(S.blk.p, 0, 40 * n, st));
   HIPCHK(ctx, hipMemsetAsync((uint8_t *)S.blk.p + 8 * n, 0xff, 8 * n, st));   // min pos: none
   HIPCHK(ctx, hipMemsetAsync(S.cnt.p, 0, 8 * CV_NCNT, st));
-  HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, st));
   SYNCCHK(ctx, hipStreamSynchronize(st));
-  S.base_rec = 0;
   S.scanned = false;
   return MH_OK;
 }
@@ -317,7 +314,7 @@ int32_t cov_clear(mh_ctx *ctx) {
 int32_t cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_t block_len) {
   CovState &S = ctx->cov;
   if (block_len < 1) return arg_fail(ctx, MH_E_ARG, "block_len must be at least 1");
-  S.begun = false;
+  S.ses.begun = false;
   S.n_refs = n_refs;
   S.n_vis = std::min(n_refs, CV_REF);
   S.block_len = block_len;
@@ -341,46 +338,33 @@ int32_t cov_begin(mh_ctx *ctx, int32_t n_refs, const int64_t *lengths, int64_t b
   MH_TRY(ensure(ctx, S.track, 4 * (size_t)std::max<int64_t>(S.n_cells, 1)));
   MH_TRY(ensure(ctx, S.blk, 40 * (size_t)std::max<int64_t>(S.n_blk, 1)));
   MH_TRY(ensure(ctx, S.cnt, 64));
-  MH_TRY(ensure(ctx, S.err, 64));
   HIPCHK(ctx, hipMemcpyAsync(S.tab.p, tab, sizeof tab, hipMemcpyHostToDevice, ctx->stream));
   MH_TRY(cov_clear(ctx));   // (waits: `tab` is on this frame)
-  S.begun = true;
+  S.ses.begun = true;
   return MH_OK;
 }
 
 int32_t cov_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
-  CovState &S = ctx->cov;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_cov_begin first");
-  if (n == 0) return MH_OK;
   MH_TRY(cov_room(ctx, n));
-  StagedRecs d;
-  MH_TRY(stage_records(ctx, S.stage, recs, len, roff, n, S.base_rec, &d));
-  MH_TRY(cov_launch(ctx, d.recs, d.roff, n, d.avail));
-  return stage_queued(ctx, S.stage, d.slot);
+  return session_add_records(ctx, ctx->cov.ses, recs, len, roff, n,
+                             [ctx](const RecChunk &c) { return cov_launch(ctx, c); });
 }
 
 int32_t cov_add_store(mh_ctx *ctx) {
   CovState &S = ctx->cov;
-  BamStore &B = ctx->bam;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_cov_begin first");
-  if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
-  if ((int64_t)B.ref_len.size() != S.n_refs) return arg_fail(ctx, MH_E_STATE, "the store's references are not the session's");
-  for (int c = 0; c < S.n_vis; c++)
-    if (B.ref_len[c] != S.ln[c]) return arg_fail(ctx, MH_E_STATE, "the store's reference lengths are not the session's");
-  if (B.n_rec == 0) return MH_OK;
-  if (B.spilled > 0)
-    return arg_fail(ctx, MH_E_STATE, "the record store has spilled to the host (mh_bam_set_capacity): use its BAM file");
-  MH_TRY(cov_room(ctx, B.n_rec));
-  const uint8_t *recs = (const uint8_t *)(B.direct ? B.srecs.p : B.recs.p);
-  const int64_t *roff = (const int64_t *)(B.direct ? B.soff.p : B.roff.p);
-  MH_TRY(cov_launch(ctx, recs, roff, B.n_rec, B.bytes));
-  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return MH_OK;
+  const BamStore &B = ctx->bam;
+  if (S.ses.begun && B.refs_set) {   // (else session_add_store says which of the two is missing)
+    if ((int64_t)B.ref_len.size() != S.n_refs) return arg_fail(ctx, MH_E_STATE, "the store's references are not the session's");
+    for (int c = 0; c < S.n_vis; c++)
+      if (B.ref_len[c] != S.ln[c]) return arg_fail(ctx, MH_E_STATE, "the store's reference lengths are not the session's");
+    MH_TRY(cov_room(ctx, B.n_rec));
+  }
+  return session_add_store(ctx, S.ses, [ctx](const RecChunk &c) { return cov_launch(ctx, c); });
 }
 
 int32_t cov_gc(mh_ctx *ctx, int32_t ref_index, int32_t contig_id) {
   CovState &S = ctx->cov;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_cov_begin first");
+  MH_TRY(session_begun(ctx, S.ses));
   if (ref_index < 0 || ref_index >= S.n_vis) return arg_fail(ctx, MH_E_ARG, "not one of the session's visited contigs");
   auto it = ctx->contigs.find(contig_id);
   if (it == ctx->contigs.end()) return arg_fail(ctx, MH_E_ARG, "no such uploaded contig");
@@ -402,21 +386,12 @@ int32_t cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc
                    int64_t *min_pos, int64_t *max_end, int64_t n_blocks, int64_t *counts) {
   CovState &S = ctx->cov;
   hipStream_t st = ctx->stream;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_cov_begin first");
+  MH_TRY(session_begun(ctx, S.ses));
   if (ref_index < 0 || ref_index >= S.n_vis) return arg_fail(ctx, MH_E_ARG, "not one of the session's visited contigs");
   const int64_t b0 = S.bbase[ref_index], nb = S.bbase[ref_index + 1] - b0;
   if (n_blocks != nb) return arg_fail(ctx, MH_E_ARG, "the contig has " + std::to_string(nb) + " blocks");
-  uint64_t herr = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&herr, S.err.p, 8, hipMemcpyDeviceToHost, st));
-  SYNCCHK(ctx, hipStreamSynchronize(st));
   std::string failed;   // the arrays are still filled: the sums of the calls before the failing one
-  if (herr != ~(uint64_t)0) {
-    static const char *what[] = {"", "fields do not fit the record", "tid outside the header's references",
-                                 "pos outside its reference"};
-    const int kind = (int)(herr & 15);
-    failed = "gc-cov: record " + std::to_string(herr >> 4) + ": " +
-             (kind >= 1 && kind <= 3 ? what[kind] : "unknown failure");
-  }
+  MH_TRY(session_failed(ctx, S.ses, &failed));
   const CovBlk b = cov_blk(S);
   if (!S.scanned && S.n_blk > 0) {
     const int64_t np = scan_partials_count(S.n_cells);
@@ -452,15 +427,14 @@ int32_t cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc
 }
 
 int32_t cov_reset(mh_ctx *ctx) {
-  if (!ctx->cov.begun) return arg_fail(ctx, MH_E_STATE, "call mh_cov_begin first");
+  MH_TRY(session_begun(ctx, ctx->cov.ses));
   return cov_clear(ctx);
 }
 
 void cov_release(CovState &S) {
-  release(S.track); release(S.depth); release(S.blk); release(S.cnt); release(S.err); release(S.desc);
+  release(S.track); release(S.depth); release(S.blk); release(S.cnt); release(S.desc);
   release(S.partials); release(S.tab);
-  stage_release(S.stage);
-  S.begun = false;
+  session_release(S.ses);
 }
 
 }  // namespace mh

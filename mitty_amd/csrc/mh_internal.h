@@ -219,40 +219,29 @@ struct BamStore {
   std::string spill_dir;       // mh_bam_set_spill_dir: spill to files there (the page cache, not anonymous memory)
 };
 
-// Host BAM records on their way to the device, shared by the sessions that take records from the host reader
-// (mh_score.hip, mh_model.hip, mh_cov.hip): two page-locked buffers, so chunk k + 1 is checked and copied while chunk k is worked on.
-struct RecStage {
-  DevBuf in[2];                // the chunk on the device: record offsets, then the records
-  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked staging, one per chunk in flight
-  size_t pin_cap[2] = {0, 0};
-  hipEvent_t ev[2] = {nullptr, nullptr};  // after the kernels of the chunk staged in pin[k]
-  bool ev_set[2] = {false, false};
-  int cur = 0;
-};
-struct StagedRecs {
-  const uint8_t *recs;         // device: the records, 64 zero bytes behind them
-  const int64_t *roff;         // device: n + 1 offsets from recs
-  int64_t avail;               // bytes readable at recs
-  int slot;
-};
+}  // namespace mh
+
+#include "mh_recs.h"   // RecStage, RecSession, RecChunk: the record sessions' shared core
+
+namespace mh {
+
+extern const RecTexts SCORE_TEXTS, MODEL_TEXTS, BQ_TEXTS, COV_TEXTS;   // each beside its session's kernels
 
 // Alignment scorer (mh_score.hip): both matrices and the counts of one scoring session, resident until read back.
 struct ScoreState {
-  bool begun = false;
+  RecSession ses{SCORE_TEXTS};
   int32_t max_d = 0, max_v = 0, strict = 0, n_refs = 0, plen = 0;
   int64_t n_mq = 0, n_dv = 0, n_all = 0;   // u64 cells of mq_mat, d_err_mat, and both + the 4 counts
   DevBuf acc, delta;           // [mq_mat | d_err_mat | counts]: the session's sums / the chunk being scored
-  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
   DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
-  RecStage stage;
-  int64_t base_rec = 0;        // records given to earlier calls (names a failing record)
 };
 
 // Read-model builder (mh_model.hip, bam2illumina): the session's histograms, resident until read back.  The `bq`
 // session is a second one whose tables are the visited contigs (by_ref) instead of the mates.
 struct ModelState {
   static constexpr int N_REF = 24;   // refs[:24]: only the header's first 24 @SQ are visited
-  bool begun = false;
+  RecSession ses;
+  explicit ModelState(const RecTexts &t) : ses(t) {}
   int32_t n_refs = 0, every = 1, min_mq = 0, max_bq = 0, max_bp = 0, max_tlen = 0;
   int32_t n_tab = 2;                 // bq tables: the two mates, or N_REF contigs (by_ref)
   bool by_ref = false;
@@ -260,17 +249,14 @@ struct ModelState {
   int64_t n_bq = 0, n_all = 0;       // u64 cells of bq_mat; of everything
   // [bq_mat | tlen | 6 counts, INT32_MAX - min_rlen, max_rlen | records per refID (N_REF)]: the session's / the chunk's
   DevBuf acc, delta;
-  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
   DevBuf desc;                 // per record of the chunk: where its qualities are, l_seq, mate and strand
   DevBuf tile_ord;             // every > 1: per 256-record tile and refID the ordinal of the tile's first such record
-  RecStage stage;
-  int64_t base_rec = 0;
 };
 
 // gc-cov (mh_cov.hip): the depth track over the visited contigs and the per-block sums of one session.
 struct CovState {
   static constexpr int N_REF = ModelState::N_REF;
-  bool begun = false;
+  RecSession ses{COV_TEXTS};
   int32_t n_refs = 0, n_vis = 0;
   int64_t block_len = 0;
   int64_t ln[N_REF] = {0}, cbase[N_REF + 1] = {0}, bbase[N_REF + 1] = {0};   // lengths; first cell / block of a contig
@@ -278,13 +264,10 @@ struct CovState {
   DevBuf track, depth;         // i32 per cell: +1 at pos, -1 at min(end, LN); its inclusive scan (at result)
   DevBuf blk;                  // per block: span sum u64 | min pos u64 | max end u64 | covered i64 | nN u32 | nGC u32
   DevBuf cnt;                  // u64[6]: seen, used, skipped unplaced / ref / flag / nospan
-  DevBuf err;                  // u64: min over failing records of (record index << 4 | kind), ~0 = none
   DevBuf desc;                 // per record of the chunk: class, contig, pos, end
   DevBuf partials;             // the scan's
   DevBuf tab;                  // i64: ln[N_REF] | cbase[N_REF + 1] | bbase[N_REF + 1] for the kernels
   bool scanned = false;        // depth and the covered counts hold the track as it is now
-  RecStage stage;
-  int64_t base_rec = 0;
 };
 
 struct StageTime {
@@ -458,7 +441,7 @@ struct mh_ctx {
   // mq-plot / derr-plot scoring session
   mh::ScoreState score;
   // bam2illumina session; bq session (the same passes, a table per contig)
-  mh::ModelState model, bq;
+  mh::ModelState model{mh::MODEL_TEXTS}, bq{mh::BQ_TEXTS};
   // gc-cov session
   mh::CovState cov;
 };
@@ -630,14 +613,6 @@ int32_t score_add_store(mh_ctx *ctx);
 int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
 int32_t score_reset(mh_ctx *ctx);
 void score_release(ScoreState &S);
-// the staging half of a session's add_records (mh_score.hip): the n records checked as the reader checks them
-// (bam_record_ok; a failure names record base_rec + i), copied with their offsets into the free page-locked buffer and
-// queued for upload; the caller queues its kernels on ctx->stream, then calls stage_queued(out->slot)
-int32_t stage_records(mh_ctx *ctx, RecStage &G, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n,
-                      int64_t base_rec, StagedRecs *out);
-int32_t stage_queued(mh_ctx *ctx, RecStage &G, int slot);
-int32_t stage_init(mh_ctx *ctx, RecStage &G);   // its events exist; the chunks in flight are done
-void stage_release(RecStage &G);
 // read-model histograms (mh_model.hip)
 int32_t model_begin(mh_ctx *ctx, ModelState &S, int32_t n_refs, int32_t every, int32_t min_mq, int32_t max_bq,
                     int32_t max_bp, int32_t max_tlen, bool by_ref);

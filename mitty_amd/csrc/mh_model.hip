@@ -8,7 +8,7 @@
 //                  template length, min / max l_seq; a 16-byte descriptor per used record (where its qualities are)
 //     -> k_model_hist   wave per record, lane per base position, coalesced quality bytes into 32-bit LDS counters
 //                  bq[position][quality] of ONE mate; flushed once per workgroup with 64-bit global atomics
-//     -> k_model_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
+//     -> session_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
 //
 // The same passes serve `bq` (reference mitty/empirical/bq.py:20-35, per contig by :38-54): a second ModelState whose
 // table selector is the record's refID instead of its mate (by_ref), 24 tables of 500 x 100, no template lengths.
@@ -31,6 +31,15 @@
 #include "mh_scan.h"
 
 namespace mh {
+
+static constexpr RecTexts model_texts(const char *label) {
+  return {label, "call the session's begin first",
+          "the record store has spilled to the host (mh_bam_set_capacity): use its BAM file",
+          {"", "fields do not fit the record", "tid outside the header's references", "l_seq is 0 (no qualities)",
+           "read longer than max_bp", "base quality of max_bq or more (0xff: no qualities stored)"}};
+}
+const RecTexts MODEL_TEXTS = model_texts("read model"), BQ_TEXTS = model_texts("bq");
+
 namespace {
 
 constexpr int MD_REF = ModelState::N_REF;
@@ -60,17 +69,11 @@ struct ModelArgs {
   int64_t base_rec;
 };
 
-__device__ __forceinline__ uint32_t md16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-__device__ __forceinline__ uint32_t md32(const uint8_t *p) {
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-
 // refID of record t when its fixed fields are readable and it is one of the visited contigs, else -1
 __device__ __forceinline__ int32_t md_ref(const ModelArgs &a, int64_t t) {
-  if (t >= a.n) return -1;
-  const int64_t s = a.roff[t], e = a.roff[t + 1];
-  if (e - s < 36 || s < 0 || e > a.avail) return -1;
-  const int32_t tid = (int32_t)md32(a.recs + s + 4);
+  int64_t s, size;
+  if (t >= a.n || !rec_span(a.roff, t, a.avail, &s, &size)) return -1;
+  const int32_t tid = (int32_t)le32(a.recs + s + 4);
   return tid >= 0 && tid < a.n_refs && tid < MD_REF ? tid : -1;
 }
 
@@ -153,15 +156,14 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
     int seen = 0, used = 0, sk_unpl = 0, sk_ref = 0, sk_every = 0, sk_flag = 0;
     ModelDesc d{-1, 0, 0};
     if (t < a.n) {
-      const int64_t s = a.roff[t], e = a.roff[t + 1];
-      const int64_t size = e - s;
+      int64_t s, size;
       seen = 1;
-      if (size < 36 || s < 0 || e > a.avail) {
+      if (!rec_span(a.roff, t, a.avail, &s, &size)) {
         kind = ME_STRUCT;
       } else {
         const uint8_t *p = a.recs + s;
-        const int32_t tid = (int32_t)md32(p + 4);
-        const int32_t mapq = p[13], flag = (int32_t)md16(p + 18);
+        const int32_t tid = (int32_t)le32(p + 4);
+        const int32_t mapq = p[13], flag = (int32_t)le16(p + 18);
         if (tid < 0) {
           sk_unpl = 1;   // fetch(reference=SN) never yields these
         } else if (tid >= a.n_refs) {
@@ -173,8 +175,8 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
         } else if (flag > 255) {
           sk_flag = 1;
         } else {
-          const int64_t l_seq = (int64_t)md32(p + 20);
-          const int64_t qoff = 36 + (int64_t)p[12] + 4 * (int64_t)md16(p + 16) + (l_seq + 1) / 2;
+          const int64_t l_seq = (int64_t)le32(p + 20);
+          const int64_t qoff = 36 + (int64_t)p[12] + 4 * (int64_t)le16(p + 16) + (l_seq + 1) / 2;
           if (l_seq == 0) kind = ME_EMPTY;           // query_qualities is None
           else if (l_seq > a.max_bp) kind = ME_LONG;  // bq_mat's second index
           else if (qoff + l_seq > size) kind = ME_STRUCT;
@@ -184,13 +186,13 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
             d.q = s + qoff;
             d.len = L;
             d.bits = (a.by_ref ? tid : ((flag & 0x40) ? 0 : 1)) << 1 | ((flag & 0x10) ? 1 : 0);
-            int64_t T = (int64_t)(int32_t)md32(p + 32);
+            int64_t T = (int64_t)(int32_t)le32(p + 32);
             if (T < 0) T = -T;
             if (mapq >= a.min_mq && mapq != 255 && (flag & 0x80) && T < a.max_tlen) tcell = (int32_t)T;
           }
         }
       }
-      if (kind) atomicMin(a.err, ((unsigned long long)(a.base_rec + t) << 4) | (unsigned long long)kind);
+      if (kind) rec_fail(a.err, a.base_rec + t, kind);
       a.desc[t] = d;
     }
     {
@@ -211,14 +213,7 @@ __global__ void __launch_bounds__(256) k_model_head(ModelArgs a) {
     if (tlen_lds) {
       if (tcell >= 0) atomicAdd(&l_tlen[tcell], 1u);
     } else {   // one global add per distinct template length among the wave's lanes
-      uint64_t pend = __ballot(tcell >= 0);
-      while (pend) {
-        const int leader = __ffsll((unsigned long long)pend) - 1;
-        const int32_t lc = __shfl(tcell, leader, 64);
-        const uint64_t m = __ballot(tcell == lc);
-        if (lane == leader) atomicAdd(&a.tlen[lc], (unsigned long long)__popcll(m));
-        pend &= ~m;
-      }
+      wave_distinct(tcell, lane, [&](int32_t lc, uint32_t c) { atomicAdd(&a.tlen[lc], (unsigned long long)c); });
     }
   }
   __syncthreads();
@@ -264,7 +259,7 @@ __global__ void __launch_bounds__(1024) k_model_hist(ModelArgs a) {
         for (int k = 0; k < 4; k++) {
           if (b[k] == 0x100u) continue;
           if (b[k] >= (uint32_t)a.max_bq)   // bq_mat's third index (0xff: the record carries no qualities)
-            atomicMin(a.err, ((unsigned long long)(a.base_rec + batch * 64 + j) << 4) | (unsigned long long)ME_QUAL);
+            rec_fail(a.err, a.base_rec + batch * 64 + j, ME_QUAL);
           else
             atomicAdd(&tab[(i0 + 64 * k - p0) * a.max_bq + (int32_t)b[k]], 1u);
         }
@@ -277,21 +272,11 @@ __global__ void __launch_bounds__(1024) k_model_hist(ModelArgs a) {
     if (tab[i]) atomicAdd(&out[i], (unsigned long long)tab[i]);
 }
 
-// cells [i_max, i_max + 2) are maxima (INT32_MAX - min l_seq, max l_seq), every other cell is a sum
-__global__ void k_model_commit(const unsigned long long *delta, unsigned long long *acc, int64_t n, int64_t i_max,
-                               const unsigned long long *err) {
-  if (*err != ~0ull) return;   // a record failed: nothing of this chunk, or of any later one, is kept
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    if (!delta[i]) continue;
-    if (i == i_max || i == i_max + 1) acc[i] = max(acc[i], delta[i]);
-    else acc[i] += delta[i];
-  }
-}
-
 // the chunk's sums zeroed, the passes over the records, the sums committed; all queued on the context's stream
-int32_t model_launch(mh_ctx *ctx, ModelState &S, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail,
-                     int32_t n_refs) {
+int32_t model_launch(mh_ctx *ctx, ModelState &S, const RecChunk &c) {
   hipStream_t st = ctx->stream;
+  const int64_t n = c.n;
+  const int32_t n_refs = c.store ? (int32_t)c.store->ref_names.size() : S.n_refs;
   const int64_t tiles = (n + 255) / 256;
   MH_TRY(ensure(ctx, S.desc, sizeof(ModelDesc) * (size_t)n));
   if (S.every > 1) MH_TRY(ensure(ctx, S.tile_ord, sizeof(uint64_t) * MD_REF * (size_t)tiles));
@@ -307,10 +292,10 @@ int32_t model_launch(mh_ctx *ctx, ModelState &S, const uint8_t *recs, const int6
   const int busy = S.by_ref ? S.n_slab : parts;
   int64_t wgp = std::min<int64_t>((batches + 15) / 16, std::max<int64_t>(1, (ctx->max_cu + busy - 1) / busy));
   wgp = std::max<int64_t>(wgp, (n >> 31) + 1);
-  ModelArgs a{recs, roff, n, avail, n_refs, S.every, S.min_mq, S.max_bq, S.max_bp, S.max_tlen, S.slab_bp, S.n_slab,
+  ModelArgs a{c.recs, c.roff, n, c.avail, n_refs, S.every, S.min_mq, S.max_bq, S.max_bp, S.max_tlen, S.slab_bp, S.n_slab,
               (int32_t)wgp, S.by_ref ? 1 : 0, d, d + o_tlen, d + o_cnt, d + o_ref,
               (const unsigned long long *)S.acc.p + o_ref, (unsigned long long *)S.tile_ord.p,
-              (ModelDesc *)S.desc.p, (unsigned long long *)S.err.p, S.base_rec};
+              (ModelDesc *)S.desc.p, (unsigned long long *)S.ses.err.p, c.base_rec};
   const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
   if (S.every > 1) {
     hipLaunchKernelGGL(k_model_refcount, dim3((unsigned)grid), dim3(256), 0, st, a);
@@ -322,20 +307,14 @@ int32_t model_launch(mh_ctx *ctx, ModelState &S, const uint8_t *recs, const int6
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_model_hist, dim3((unsigned)(wgp * parts)), dim3(1024), 0, st, a);
   HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_model_commit, dim3(grid_for(S.n_all, 256, 1024)), dim3(256), 0, st,
-                     (const unsigned long long *)S.delta.p, (unsigned long long *)S.acc.p, S.n_all, o_cnt + 6,
-                     (const unsigned long long *)S.err.p);
-  HIPCHK(ctx, hipGetLastError());
-  S.base_rec += n;
-  return MH_OK;
+  // cells o_cnt + 6 and + 7 are maxima (INT32_MAX - min l_seq, max l_seq), every other cell is a sum
+  return session_commit(ctx, S.ses, S.delta, S.acc, S.n_all, o_cnt + 6);
 }
 
 int32_t model_clear(mh_ctx *ctx, ModelState &S) {
-  MH_TRY(stage_init(ctx, S.stage));
+  MH_TRY(session_clear(ctx, S.ses));
   HIPCHK(ctx, hipMemsetAsync(S.acc.p, 0, sizeof(uint64_t) * S.n_all, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, ctx->stream));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  S.base_rec = 0;
   return MH_OK;
 }
 
@@ -350,7 +329,7 @@ int32_t model_begin(mh_ctx *ctx, ModelState &S, int32_t n_refs, int32_t every, i
   if (max_bp < 1 || max_tlen < 1) return arg_fail(ctx, MH_E_ARG, "max_bp and max_tlen must be positive");
   if (n_tab * (int64_t)max_bp * max_bq >= INT32_MAX) return arg_fail(ctx, MH_E_ARG, "bq_mat of 2^31 cells or more");
   if (max_tlen == INT32_MAX) return arg_fail(ctx, MH_E_ARG, "tlen histogram of 2^31 cells or more");
-  S.begun = false;
+  S.ses.begun = false;
   S.n_refs = n_refs;
   S.every = every;
   S.min_mq = min_mq;
@@ -363,56 +342,30 @@ int32_t model_begin(mh_ctx *ctx, ModelState &S, int32_t n_refs, int32_t every, i
   S.n_slab = (max_bp + S.slab_bp - 1) / S.slab_bp;
   S.n_bq = n_tab * (int64_t)max_bp * max_bq;
   S.n_all = S.n_bq + max_tlen + MD_NCNT + MD_REF;
-  MH_TRY(stage_init(ctx, S.stage));
   MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
-  MH_TRY(ensure(ctx, S.err, 64));
   MH_TRY(model_clear(ctx, S));
-  S.begun = true;
+  S.ses.begun = true;
   return MH_OK;
 }
 
 int32_t model_add_records(mh_ctx *ctx, ModelState &S, const uint8_t *recs, int64_t len, const int64_t *roff,
                           int64_t n) {
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
-  if (n == 0) return MH_OK;
-  StagedRecs d;
-  MH_TRY(stage_records(ctx, S.stage, recs, len, roff, n, S.base_rec, &d));
-  MH_TRY(model_launch(ctx, S, d.recs, d.roff, n, d.avail, S.n_refs));
-  return stage_queued(ctx, S.stage, d.slot);
+  return session_add_records(ctx, S.ses, recs, len, roff, n,
+                             [ctx, &S](const RecChunk &c) { return model_launch(ctx, S, c); });
 }
 
+// (the store's own order stands for the file's)
 int32_t model_add_store(mh_ctx *ctx, ModelState &S) {
-  BamStore &B = ctx->bam;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
-  if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
-  if (B.n_rec == 0) return MH_OK;
-  if (B.spilled > 0)
-    return arg_fail(ctx, MH_E_STATE, "the record store has spilled to the host (mh_bam_set_capacity): use its BAM file");
-  // the store's own order stands for the file's: input order, or coordinate order after a direct sorted write
-  const uint8_t *recs = (const uint8_t *)(B.direct ? B.srecs.p : B.recs.p);
-  const int64_t *roff = (const int64_t *)(B.direct ? B.soff.p : B.roff.p);
-  MH_TRY(model_launch(ctx, S, recs, roff, B.n_rec, B.bytes, (int32_t)B.ref_names.size()));
-  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return MH_OK;
+  return session_add_store(ctx, S.ses, [ctx, &S](const RecChunk &c) { return model_launch(ctx, S, c); });
 }
 
 // the session's work waited for; the first failing record, if any, as MH_E_ARG
 static int32_t model_wait(mh_ctx *ctx, ModelState &S) {
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
-  uint64_t herr = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&herr, S.err.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (herr != ~(uint64_t)0) {
-    static const char *what[] = {"", "fields do not fit the record", "tid outside the header's references",
-                                 "l_seq is 0 (no qualities)", "read longer than max_bp",
-                                 "base quality of max_bq or more (0xff: no qualities stored)"};
-    const int kind = (int)(herr & 15);
-    return arg_fail(ctx, MH_E_ARG, std::string(S.by_ref ? "bq" : "read model") + ": record " +
-                                       std::to_string(herr >> 4) + ": " +
-                                       (kind >= 1 && kind <= 5 ? what[kind] : "unknown failure"));
-  }
-  return MH_OK;
+  MH_TRY(session_begun(ctx, S.ses));
+  std::string failed;
+  MH_TRY(session_failed(ctx, S.ses, &failed));
+  return failed.empty() ? MH_OK : arg_fail(ctx, MH_E_ARG, failed);
 }
 
 int32_t model_result(mh_ctx *ctx, ModelState &S, uint64_t *bq_mat, uint64_t *tlen_mat, int64_t *counts) {
@@ -444,14 +397,13 @@ int32_t model_result_table(mh_ctx *ctx, ModelState &S, int32_t tab, uint64_t *ma
 }
 
 int32_t model_reset(mh_ctx *ctx, ModelState &S) {
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call the session's begin first");
+  MH_TRY(session_begun(ctx, S.ses));
   return model_clear(ctx, S);
 }
 
 void model_release(ModelState &S) {
-  release(S.acc); release(S.delta); release(S.err); release(S.desc); release(S.tile_ord);
-  stage_release(S.stage);
-  S.begun = false;
+  release(S.acc); release(S.delta); release(S.desc); release(S.tile_ord);
+  session_release(S.ses);
 }
 
 }  // namespace mh

@@ -7,7 +7,7 @@
 //                  tid, d_err, then both matrices from the one pass:
 //                    mq_mat[mapq, d_err + max_d]          u64[100][2 max_d + 1]
 //                    d_err_mat[max_v + v, d_err + max_d]  u64[2 max_v + 2][2 max_d + 1]   (last row: empty v_list)
-//     -> k_score_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
+//     -> session_commit   the chunk's sums join the session's, unless a record of this or an earlier chunk failed
 //
 // Contention: nearly every read of a good aligner lands in (MAPQ 60, d_err 0) and (ref or SNP row, d_err 0).  Lanes of
 // a wave with equal cells are combined into one add (ballot + popcount); the d_err = 0 column of both matrices is
@@ -19,10 +19,17 @@
 #include <algorithm>
 #include <cstring>
 
-#include "mh_bamread.h"
 #include "mh_internal.h"
 
 namespace mh {
+
+const RecTexts SCORE_TEXTS = {
+    "scoring", "call mh_score_begin first",
+    "the record store has spilled to the host (mh_bam_set_capacity): score its BAM file",
+    {"", "record shorter than its fixed fields", "tid outside the header's references",
+     "qname does not parse (readgenerate.parse_qname)", "read2 record whose qname has one read group",
+     "MAPQ of 100 or more (mq_mat has 100 rows)"}};
+
 namespace {
 
 constexpr int SC_ROW = 192;       // LDS bytes per record head (4 + 32 fixed bytes, then the name; up to 15 bytes of lead)
@@ -45,11 +52,6 @@ struct ScoreArgs {
   unsigned long long *err;
   int64_t base_rec;
 };
-
-__device__ __forceinline__ uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-__device__ __forceinline__ uint32_t rd32(const uint8_t *p) {
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
 
 // int() of q[a, b): optional sign, then digits only; values saturate at 2^40.  False when it is not such a number.
 __device__ __forceinline__ bool sc_int(const uint8_t *q, int a, int b, int64_t &v) {
@@ -89,20 +91,11 @@ __device__ __forceinline__ bool sc_vlist_ok(const uint8_t *q, int a, int b, int 
 // counters (row < lds_rows), everything else to the chunk's matrix in memory.  Called by every lane of the wave.
 __device__ __forceinline__ void wave_add(int32_t cell, int lane, int32_t ncol, int32_t zero_col, uint32_t *lds,
                                          int32_t lds_rows, unsigned long long *g) {
-  uint64_t pend = __ballot(cell >= 0);
-  while (pend) {
-    const int leader = __ffsll((unsigned long long)pend) - 1;
-    const int32_t lc = __shfl(cell, leader, 64);
-    const uint64_t m = __ballot(cell == lc);
-    if (lane == leader) {
-      const uint32_t c = (uint32_t)__popcll(m);
-      const int32_t row = lc / ncol, col = lc - row * ncol;
-      if (col == zero_col && row < lds_rows) atomicAdd(&lds[row], c);
-      else atomicAdd(&g[lc], (unsigned long long)c);
-    }
-    if (cell == lc) cell = -1;
-    pend &= ~m;
-  }
+  wave_distinct(cell, lane, [&](int32_t lc, uint32_t c) {
+    const int32_t row = lc / ncol, col = lc - row * ncol;
+    if (col == zero_col && row < lds_rows) atomicAdd(&lds[row], c);
+    else atomicAdd(&g[lc], (unsigned long long)c);
+  });
 }
 
 __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
@@ -156,8 +149,8 @@ __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
           const uint8_t *rp = rows + threadIdx.x * SC_ROW + (s - c0);
           if (36 + (int64_t)rp[12] <= rb) lp = rp;   // a name longer than its row is read from memory
         }
-        const int32_t tid = (int32_t)rd32(lp + 4), pos = (int32_t)rd32(lp + 8);
-        const int32_t mapq = lp[13], flag = (int32_t)rd16(lp + 18);
+        const int32_t tid = (int32_t)le32(lp + 4), pos = (int32_t)le32(lp + 8);
+        const int32_t mapq = lp[13], flag = (int32_t)le16(lp + 18);
         int nmax = lp[12];
         if (nmax > size - 36) nmax = (int)(size - 36);
         q = lp + 36;
@@ -262,7 +255,7 @@ __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
           }
         }
       }
-      if (kind) atomicMin(a.err, ((unsigned long long)(a.base_rec + t) << 4) | (unsigned long long)kind);
+      if (kind) rec_fail(a.err, a.base_rec + t, kind);
     }
     {   // the four counts: one LDS add per wave each
       const uint64_t b[4] = {__ballot(seen), __ballot(scored), __ballot(skip_tid), __ballot(skip_smp)};
@@ -303,42 +296,30 @@ __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
   if (threadIdx.x < 4 && l_cnt[threadIdx.x]) atomicAdd(&a.cnt[threadIdx.x], (unsigned long long)l_cnt[threadIdx.x]);
 }
 
-__global__ void k_score_commit(const unsigned long long *delta, unsigned long long *acc, int64_t n,
-                               const unsigned long long *err) {
-  if (*err != ~0ull) return;   // a record failed: nothing of this chunk, or of any later one, is kept
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    if (delta[i]) acc[i] += delta[i];
-}
-
-// the chunk's sums zeroed, the records scored, the sums committed; all queued on the context's stream
-int32_t score_launch(mh_ctx *ctx, const uint8_t *recs, const int64_t *roff, int64_t n, int64_t avail, const char *names,
-                     const int32_t *name_off, int32_t n_refs) {
+// the chunk's sums zeroed, the records scored, the sums committed; all queued on the context's stream.  Header names:
+// the store's own on that path, the session's otherwise
+int32_t score_launch(mh_ctx *ctx, const RecChunk &c) {
   ScoreState &S = ctx->score;
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipMemsetAsync(S.delta.p, 0, sizeof(uint64_t) * S.n_all, st));
   unsigned long long *d = (unsigned long long *)S.delta.p;
-  ScoreArgs a{recs, roff, n, avail, names, name_off, n_refs, (const uint8_t *)S.prefix.p, S.plen, S.max_d, S.max_v,
-              S.strict, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.err.p, S.base_rec};
+  const DevBuf &names = c.store ? c.store->names : S.names, &name_off = c.store ? c.store->name_off : S.name_off;
+  ScoreArgs a{c.recs, c.roff, c.n, c.avail, (const char *)names.p, (const int32_t *)name_off.p,
+              c.store ? (int32_t)c.store->ref_names.size() : S.n_refs, (const uint8_t *)S.prefix.p, S.plen, S.max_d,
+              S.max_v, S.strict, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.ses.err.p, c.base_rec};
   // a workgroup's LDS counters are 32-bit: at most 4096 tiles (2^20 records, < 2^8 list items each) per workgroup
-  const int64_t tiles = (n + 255) / 256;
+  const int64_t tiles = (c.n + 255) / 256;
   const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
   hipLaunchKernelGGL(k_score, dim3((unsigned)grid), dim3(256), 0, st, a);
   HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_score_commit, dim3(grid_for(S.n_all, 256, 1024)), dim3(256), 0, st,
-                     (const unsigned long long *)S.delta.p, (unsigned long long *)S.acc.p, S.n_all,
-                     (const unsigned long long *)S.err.p);
-  HIPCHK(ctx, hipGetLastError());
-  S.base_rec += n;
-  return MH_OK;
+  return session_commit(ctx, S.ses, S.delta, S.acc, S.n_all, S.n_all);   // (no cell is a maximum)
 }
 
 int32_t score_clear(mh_ctx *ctx) {
   ScoreState &S = ctx->score;
-  MH_TRY(stage_init(ctx, S.stage));
+  MH_TRY(session_clear(ctx, S.ses));
   HIPCHK(ctx, hipMemsetAsync(S.acc.p, 0, sizeof(uint64_t) * S.n_all, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(S.err.p, 0xff, 8, ctx->stream));
   SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  S.base_rec = 0;
   return MH_OK;
 }
 
@@ -353,7 +334,7 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   if (max_v_len > (1 << 20)) return arg_fail(ctx, MH_E_ARG, "max_v_len must be at most 2^20");
   const int64_t ncol = 2 * (int64_t)max_d + 1;
   if ((2 * (int64_t)max_v_len + 2) * ncol >= INT32_MAX) return arg_fail(ctx, MH_E_ARG, "d_err matrix of 2^31 cells or more");
-  S.begun = false;
+  S.ses.begun = false;
   S.max_d = max_d;
   S.max_v = max_v_len;
   S.strict = strict ? 1 : 0;
@@ -373,10 +354,8 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   S.n_refs = n_refs;
   S.plen = (int32_t)pre.size();
   hipStream_t st = ctx->stream;
-  MH_TRY(stage_init(ctx, S.stage));
   MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
-  MH_TRY(ensure(ctx, S.err, 64));
   MH_TRY(ensure(ctx, S.names, cat.size() + 16));
   MH_TRY(ensure(ctx, S.name_off, sizeof(int32_t) * off.size()));
   MH_TRY(ensure(ctx, S.prefix, pre.size() + 16));
@@ -384,118 +363,26 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   HIPCHK(ctx, hipMemcpyAsync(S.name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
   if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(S.prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
   MH_TRY(score_clear(ctx));   // (synchronises: the host strings above are done with)
-  S.begun = true;
+  S.ses.begun = true;
   return MH_OK;
-}
-
-int32_t stage_init(mh_ctx *ctx, RecStage &G) {
-  for (int k = 0; k < 2; k++) {
-    if (!G.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&G.ev[k], hipEventDisableTiming));
-    if (G.ev_set[k]) {
-      HIPCHK(ctx, hipEventSynchronize(G.ev[k]));
-      G.ev_set[k] = false;
-    }
-  }
-  return MH_OK;
-}
-
-int32_t stage_records(mh_ctx *ctx, RecStage &G, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n,
-                      int64_t base_rec, StagedRecs *out) {
-  // the same structural check the reader applies: nothing malformed reaches the device
-  if (roff[0] < 0 || roff[n] > len) return arg_fail(ctx, MH_E_ARG, "record offsets outside the buffer");
-  for (int64_t i = 0; i < n; i++) {
-    std::string why;
-    if (roff[i + 1] < roff[i] || roff[i + 1] > len || !bam_record_ok(recs + roff[i], roff[i + 1] - roff[i], &why))
-      return arg_fail(ctx, MH_E_ARG, "malformed BAM record " + std::to_string(base_rec + i) + ": " +
-                                         (why.empty() ? "record offsets decrease" : why));
-  }
-  const int k = G.cur;
-  if (G.ev_set[k]) {   // the chunk staged here two calls ago has been worked through
-    HIPCHK(ctx, hipEventSynchronize(G.ev[k]));
-    G.ev_set[k] = false;
-  }
-  const int64_t bytes = roff[n] - roff[0];
-  const size_t o_recs = ((size_t)(n + 1) * 8 + 15) & ~(size_t)15, need = o_recs + (size_t)bytes + 64;
-  if (G.pin_cap[k] < need) {
-    if (G.pin[k]) (void)hipHostFree(G.pin[k]);
-    G.pin[k] = nullptr;
-    G.pin_cap[k] = 0;
-    const size_t cap = need + need / 4;
-    HIPCHK(ctx, hipHostMalloc((void **)&G.pin[k], cap, hipHostMallocDefault));
-    G.pin_cap[k] = cap;
-  }
-  int64_t *po = (int64_t *)G.pin[k];
-  for (int64_t i = 0; i <= n; i++) po[i] = roff[i] - roff[0];
-  memcpy(G.pin[k] + o_recs, recs + roff[0], (size_t)bytes);
-  memset(G.pin[k] + o_recs + bytes, 0, 64);
-  MH_TRY(ensure(ctx, G.in[k], need));
-  HIPCHK(ctx, hipMemcpyAsync(G.in[k].p, G.pin[k], need, hipMemcpyHostToDevice, ctx->stream));
-  *out = StagedRecs{(const uint8_t *)G.in[k].p + o_recs, (const int64_t *)G.in[k].p, bytes + 64, k};
-  return MH_OK;
-}
-
-int32_t stage_queued(mh_ctx *ctx, RecStage &G, int slot) {
-  HIPCHK(ctx, hipEventRecord(G.ev[slot], ctx->stream));
-  G.ev_set[slot] = true;
-  G.cur = slot ^ 1;
-  return MH_OK;
-}
-
-void stage_release(RecStage &G) {
-  for (int k = 0; k < 2; k++) {
-    release(G.in[k]);
-    if (G.pin[k]) (void)hipHostFree(G.pin[k]);
-    if (G.ev[k]) (void)hipEventDestroy(G.ev[k]);
-    G.pin[k] = nullptr;
-    G.pin_cap[k] = 0;
-    G.ev[k] = nullptr;
-    G.ev_set[k] = false;
-  }
 }
 
 int32_t score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
-  ScoreState &S = ctx->score;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
-  if (n == 0) return MH_OK;
-  StagedRecs d;
-  MH_TRY(stage_records(ctx, S.stage, recs, len, roff, n, S.base_rec, &d));
-  MH_TRY(score_launch(ctx, d.recs, d.roff, n, d.avail, (const char *)S.names.p, (const int32_t *)S.name_off.p,
-                      S.n_refs));
-  return stage_queued(ctx, S.stage, d.slot);
+  return session_add_records(ctx, ctx->score.ses, recs, len, roff, n,
+                             [ctx](const RecChunk &c) { return score_launch(ctx, c); });
 }
 
+// (the sums do not depend on the store's order)
 int32_t score_add_store(mh_ctx *ctx) {
-  ScoreState &S = ctx->score;
-  BamStore &B = ctx->bam;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
-  if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
-  if (B.n_rec == 0) return MH_OK;
-  if (B.spilled > 0)
-    return arg_fail(ctx, MH_E_STATE, "the record store has spilled to the host (mh_bam_set_capacity): score its BAM file");
-  // a direct sorted write keeps the records in coordinate order only; the sums do not depend on the order
-  const uint8_t *recs = (const uint8_t *)(B.direct ? B.srecs.p : B.recs.p);
-  const int64_t *roff = (const int64_t *)(B.direct ? B.soff.p : B.roff.p);
-  MH_TRY(score_launch(ctx, recs, roff, B.n_rec, B.bytes, (const char *)B.names.p, (const int32_t *)B.name_off.p,
-                      (int32_t)B.ref_names.size()));
-  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return MH_OK;
+  return session_add_store(ctx, ctx->score.ses, [ctx](const RecChunk &c) { return score_launch(ctx, c); });
 }
 
 int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts) {
   ScoreState &S = ctx->score;
-  if (!S.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
-  uint64_t herr = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&herr, S.err.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  SYNCCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (herr != ~(uint64_t)0) {
-    static const char *what[] = {"", "record shorter than its fixed fields", "tid outside the header's references",
-                                 "qname does not parse (readgenerate.parse_qname)",
-                                 "read2 record whose qname has one read group",
-                                 "MAPQ of 100 or more (mq_mat has 100 rows)"};
-    const int kind = (int)(herr & 15);
-    return arg_fail(ctx, MH_E_ARG, "scoring: record " + std::to_string(herr >> 4) + ": " +
-                                       (kind >= 1 && kind <= 5 ? what[kind] : "unknown failure"));
-  }
+  MH_TRY(session_begun(ctx, S.ses));
+  std::string failed;
+  MH_TRY(session_failed(ctx, S.ses, &failed));
+  if (!failed.empty()) return arg_fail(ctx, MH_E_ARG, failed);
   const uint64_t *acc = (const uint64_t *)S.acc.p;
   if (mq_mat) HIPCHK(ctx, hipMemcpyAsync(mq_mat, acc, 8 * S.n_mq, hipMemcpyDeviceToHost, ctx->stream));
   if (derr_mat) HIPCHK(ctx, hipMemcpyAsync(derr_mat, acc + S.n_mq, 8 * S.n_dv, hipMemcpyDeviceToHost, ctx->stream));
@@ -505,14 +392,13 @@ int32_t score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t 
 }
 
 int32_t score_reset(mh_ctx *ctx) {
-  if (!ctx->score.begun) return arg_fail(ctx, MH_E_STATE, "call mh_score_begin first");
+  MH_TRY(session_begun(ctx, ctx->score.ses));
   return score_clear(ctx);
 }
 
 void score_release(ScoreState &S) {
-  release(S.acc); release(S.delta); release(S.err); release(S.names); release(S.name_off); release(S.prefix);
-  stage_release(S.stage);
-  S.begun = false;
+  release(S.acc); release(S.delta); release(S.names); release(S.name_off); release(S.prefix);
+  session_release(S.ses);
 }
 
 }  // namespace mh

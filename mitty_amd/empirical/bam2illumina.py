@@ -8,32 +8,21 @@ import time
 
 import numpy as np
 
-from mitty_amd import _native, readmodel
+from mitty_amd import readmodel
+from mitty_amd.lib import bamsession
+from mitty_amd.lib.bamsession import CHUNK_BYTES
 
 logger = logging.getLogger(__name__)
-
-CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
 
 
 def count_bam(bam_fname, every=1, min_mq=0, threads=4, max_bq=94, max_bp=300, max_tlen=1000, device=0,
               chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """(bq_mat, tlen_mat, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk
   k + 1.  `threads` sizes the inflate pool; gpu_inflate: the BGZF blocks are inflated on `device` instead."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
-  try:
-    ctx = _native.Context(device)
-    try:
-      ctx.model_begin(bam.names_blob.count(b'\0'), every, min_mq, max_bq, max_bp, max_tlen)
-      while True:
-        recs, nbytes, roff, n = bam.next_raw(chunk_bytes)
-        if n == 0:
-          break
-        ctx.model_add_raw(recs, nbytes, roff, n)
-      return ctx.model_result()
-    finally:
-      ctx.close()
-  finally:
-    bam.close()
+  with bamsession.opened(bam_fname, threads, device, gpu_inflate) as (bam, ctx, _):
+    ctx.model_begin(bam.names_blob.count(b'\0'), every, min_mq, max_bq, max_bp, max_tlen)
+    bamsession.feed(bam, ctx.model_add_raw, chunk_bytes)
+    return ctx.model_result()
 
 
 def model_from_counts(bq_mat, tlen_mat, r_cnt, min_rlen, max_rlen, model_description='Test model', min_mq=0):

@@ -5,13 +5,10 @@ import logging
 import pickle
 import time
 
-from mitty_amd import _native
-from mitty_amd.benchmarking.god_aligner import seq_info
+from mitty_amd.lib import bamsession
+from mitty_amd.lib.bamsession import CHUNK_BYTES, MAX_CHROMS   # (:42)
 
 logger = logging.getLogger(__name__)
-
-CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
-MAX_CHROMS = 24          # (:42)
 
 
 def _results(ctx, sq):
@@ -25,24 +22,10 @@ def _results(ctx, sq):
 def count_bam(bam_fname, threads=4, device=0, chunk_bytes=CHUNK_BYTES, gpu_inflate=False):
   """(bq_data dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1.
   gpu_inflate: the BGZF blocks are inflated on `device` instead of on the `threads` pool."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
-  try:
-    sq = seq_info(bam.text, bam.names, bam.lengths)
-    if [(s['SN'], s['LN']) for s in sq] != list(zip(bam.names, bam.lengths)):
-      raise ValueError('the @SQ lines of the header text are not the BAM\'s reference list')
-    ctx = _native.Context(device)
-    try:
-      ctx.bq_begin(len(sq))
-      while True:
-        recs, nbytes, roff, n = bam.next_raw(chunk_bytes)
-        if n == 0:
-          break
-        ctx.bq_add_raw(recs, nbytes, roff, n)
-      return _results(ctx, sq)
-    finally:
-      ctx.close()
-  finally:
-    bam.close()
+  with bamsession.opened(bam_fname, threads, device, gpu_inflate, bamsession.header_sq) as (bam, ctx, sq):
+    ctx.bq_begin(len(sq))
+    bamsession.feed(bam, ctx.bq_add_raw, chunk_bytes)
+    return _results(ctx, sq)
 
 
 def from_store(ctx, sq):

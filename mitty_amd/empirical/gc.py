@@ -17,12 +17,11 @@ import time
 import numpy as np
 
 from mitty_amd import _native
-from mitty_amd.benchmarking.god_aligner import seq_info
+from mitty_amd.lib import bamsession
+from mitty_amd.lib.bamsession import CHUNK_BYTES, MAX_CHROMS   # (:66)
 
 logger = logging.getLogger(__name__)
 
-CHUNK_BYTES = 64 << 20   # uncompressed record bytes per upload
-MAX_CHROMS = 24          # (:66)
 DTYPE = [('gc', float), ('coverage', float)]
 # the contig id the one resident contig is uploaded under: negative, so that it is none of an Engine's regions
 # (Engine.load_region uploads region ri as contig ri >= 0); released when the counts are done
@@ -85,27 +84,17 @@ def count_bam(bam_fname, fasta_fname, block_len=10000, threads=4, device=0, chun
               gpu_inflate=False):
   """(gc_cov dict, counts) of `bam_fname`: chunk k is counted on the device while the reader inflates chunk k + 1.
   gpu_inflate: the BGZF blocks are inflated on `device` instead of on the `threads` pool."""
-  bam = _native.BamFile(bam_fname, threads=max(1, int(threads)), device=device if gpu_inflate else None)
-  try:
-    sq = seq_info(bam.text, bam.names, bam.lengths)
-    if [(s['SN'], s['LN']) for s in sq] != list(zip(bam.names, bam.lengths)):
-      raise ValueError('the @SQ lines of the header text are not the BAM\'s reference list')
+  def header_and_fasta(bam):   # (before a device is touched)
+    sq = bamsession.header_sq(bam)
     seqs = _native.read_fasta(fasta_fname, [s['SN'] for s in sq[:MAX_CHROMS]])
-    check_fasta(sq, seqs)   # (before a device is touched)
-    ctx = _native.Context(device)
-    try:
-      ctx.cov_begin(bam.lengths, block_len)
-      _upload_gc(ctx, sq, seqs)
-      while True:
-        recs, nbytes, roff, n = bam.next_raw(chunk_bytes)
-        if n == 0:
-          break
-        ctx.cov_add_raw(recs, nbytes, roff, n)
-      return _results(ctx, sq, block_len)
-    finally:
-      ctx.close()
-  finally:
-    bam.close()
+    check_fasta(sq, seqs)
+    return sq, seqs
+
+  with bamsession.opened(bam_fname, threads, device, gpu_inflate, header_and_fasta) as (bam, ctx, (sq, seqs)):
+    ctx.cov_begin(bam.lengths, block_len)
+    _upload_gc(ctx, sq, seqs)
+    bamsession.feed(bam, ctx.cov_add_raw, chunk_bytes)
+    return _results(ctx, sq, block_len)
 
 
 def from_store(ctx, sq, seqs, block_len=10000, contig_id=SCRATCH_CONTIG_ID):
