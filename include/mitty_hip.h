@@ -28,6 +28,7 @@
  *   mh_cov_add_records    gc.gc_and_coverage_for_region's pileup         mitty/empirical/gc.py:37-38, 43-59
  *   mh_cov_gc             gc.gc_and_coverage_for_region's seq.count      mitty/empirical/gc.py:32-36
  *   mh_bq_add_records     bq.bq_over_chromosome                          mitty/empirical/bq.py:20-35
+ *   mh_gc_thin            (none: the sampler's `# TODO: GC-bias goes here`) mitty/simulation/illumina.py:67
  *
  * Threading: one mh_ctx per GPU and per host thread; a context owns one HIP stream and all device buffers.
  * Calls are synchronous at return (device work is ordered on the context's stream; results copied back are
@@ -198,6 +199,27 @@ int32_t mh_templates_export(mh_ctx *ctx, int32_t tpl_id, int32_t on_device, int8
                             int64_t *pos1, int64_t cap, int64_t *n);
 int32_t mh_templates_import(mh_ctx *ctx, int32_t tpl_id, int32_t on_device, const int8_t *fo0, const int64_t *pos0,
                             const int64_t *pos1, int64_t n, int32_t rlen);
+/* GC-bias thinning (generate-reads --gc-bias; the hole the reference marks `# TODO: GC-bias goes here`,
+ * mitty/simulation/illumina.py:67).  The rule is this library's own, as the Philox corruption stream's is:
+ *   accept[b], b = 0 .. 100: T[b] = min(2^32, floor(w[b] * 2^32)) of a curve's weight w[b] in [0, 1]
+ *   template t (its index in the set before thinning, 64-bit) of set tpl_id on haplotype `slot`:
+ *     start = clamp(pos0[t] - p_min, 0, hap_len), end = clamp(pos1[t] + rlen - p_min, start, hap_len), L = end - start
+ *     g   = bytes of hap[start:end] equal to 'G' or 'C' (upper case only, as gc-cov counts; every other byte, 'N' and
+ *           lower case included, counts in L only)
+ *     bin = (100 * g) / L in integers, 0 when L == 0
+ *     u   = word 0 of philox4x32_10(counter (t & 0xffffffff, t >> 32, 0, c3), key (k0, k1)), k0 = seed & 0xffffffff,
+ *           k1 = unit_key & 0xffffffff, c3 = ((seed >> 32) ^ (unit_key >> 32) ^ 0x67636269) & 0xffffffff
+ *     kept iff u < T[bin]
+ * Kept templates keep their relative order; fo0, pos0, pos1 (and the start nodes a sampled set carries) are compacted
+ * together, so everything after the call (the N filter, the read numbering, the corruption stream's template index,
+ * slices across ranks) sees the thinned set only.  Once per set and before any emission of it: MH_E_STATE for a set
+ * with a prepared or queued emission (and for an unknown set or an empty slot), MH_E_ARG for a threshold above 2^32.
+ * Waits for the result: *out_n = templates kept (the set's new size; an empty set is valid), bin_seen[101] /
+ * bin_kept[101] (either may be null) = templates seen / kept per bin. */
+#define MH_GC_BINS 101
+int32_t mh_gc_thin(mh_ctx *ctx, int32_t tpl_id, int32_t slot, const uint64_t *accept /*[101]*/, uint64_t seed,
+                   uint64_t unit_key, int64_t *out_n, int64_t *bin_seen /*[101] or NULL*/,
+                   int64_t *bin_kept /*[101] or NULL*/);
 
 /* ---- read emission ------------------------------------------------------------------------------------- */
 /* Turn the current templates into FASTQ text for both files, appended to the device arenas.

@@ -20,7 +20,7 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_selftest_scan_fault', 'mh_selftest_scan', 'mh_selftest_sort', 'mh_selftest_bgzf',
            'mh_read_model_params', 'mh_work_units', 'mh_upload_contig', 'mh_release_contig', 'mh_build_haplotype', 'mh_upload_variants', 'mh_build_haplotype_vset', 'mh_build_haplotypes_vset', 'mh_prefetch_haplotypes_vset', 'mh_release_variants', 'mh_get_nodes', 'mh_get_haplotype_aux',
            'mh_release_haplotype', 'mh_expand_variant', 'mh_sample_templates', 'mh_sample_templates_span', 'mh_set_templates',
-           'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
+           'mh_get_templates', 'mh_templates_export', 'mh_templates_import', 'mh_gc_thin', 'mh_emit_reads', 'mh_emit_prepare', 'mh_emit_reads_async', 'mh_emit_collect', 'mh_output_size', 'mh_output_fetch', 'mh_output_reset', 'mh_host_alloc', 'mh_host_free', 'mh_device_cache_trim', 'mh_device_live_bytes',
            'mh_read_batch', 'mh_set_corruption', 'mh_set_corruption_stream', 'mh_get_corruption_stream', 'mh_stage_times', 'mh_enable_timing', 'mh_sample_units', 'mh_sample_units_async', 'mh_templates_count',
            'mh_use_templates', 'mh_release_templates', 'mh_mt_window_at', 'mh_fixup_count', 'mh_set_emit_mode', 'mh_set_decode_mode',
            'mh_emit_reads_range', 'mh_emit_measure', 'mh_count_kept', 'mh_bam_set_refs', 'mh_bam_add_fastq', 'mh_bam_add_output',
@@ -37,6 +37,8 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
 
 
 MODEL_NO_RLEN = (1 << 63) - 1   # MH_MODEL_NO_RLEN: counts[6] of mh_model_result when no record was used
+GC_BINS = 101                   # MH_GC_BINS: GC percent bins of mh_gc_thin
+MASK64 = (1 << 64) - 1
 COV_NO_POS = (1 << 63) - 1      # MH_COV_NO_POS: min_pos of a block no record met
 BQ_MAX_BP, BQ_MAX_BQ = 500, 100   # MH_BQ_MAX_BP, MH_BQ_MAX_BQ: bq.py:28
 
@@ -200,6 +202,7 @@ def lib():
   _sig(L, 'mh_set_corruption', [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_u64])
   _sig(L, 'mh_templates_export', [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, P_i64])
   _sig(L, 'mh_templates_import', [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32])
+  _sig(L, 'mh_gc_thin', [c_vp, c_i32, c_i32, c_vp, c_u64, c_u64, P_i64, c_vp, c_vp])
   _sig(L, 'mh_set_corruption_stream', [c_vp, c_i32, c_u64, c_vp, c_i32])
   _sig(L, 'mh_get_corruption_stream', [c_vp, c_vp, ctypes.POINTER(c_i32), P_i64])
   _sig(L, 'mh_stage_times', [c_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_dbl), c_i32,
@@ -1282,6 +1285,19 @@ class Context:
     b = np.ascontiguousarray(pos0, dtype=np.int64)
     c = np.ascontiguousarray(pos1, dtype=np.int64)
     self._chk(self._L.mh_templates_import(self._h, int(tpl_id), 0, _ptr(a), _ptr(b), _ptr(c), int(n), int(rlen)))
+
+  def gc_thin(self, tpl_id, slot, accept, seed, unit_key):
+    """Thin template set tpl_id by the GC content of the bytes of haplotype `slot` each template spans (mh_gc_thin;
+    accept: the curve's uint64[101] thresholds, simulation.gcbias.thresholds).  Once, before any emission of the set.
+    Returns (n kept, seen[101], kept[101])."""
+    acc = np.ascontiguousarray(accept, dtype=np.uint64)
+    if acc.shape != (GC_BINS,):
+      raise ValueError('gc_thin: {} thresholds needed, got an array of shape {}'.format(GC_BINS, acc.shape))
+    n = c_i64()
+    seen, kept = np.zeros(GC_BINS, np.int64), np.zeros(GC_BINS, np.int64)
+    self._chk(self._L.mh_gc_thin(self._h, int(tpl_id), int(slot), _ptr(acc), int(seed) & MASK64, int(unit_key) & MASK64,
+                                 ctypes.byref(n), _ptr(seen), _ptr(kept)))
+    return n.value, seen, kept
 
   def set_corruption_stream(self, rng_mode, seed=0, key=None, pos=624):
     """mh_corrupt_fastq's word source: MH_RNG_PHILOX, or MH_RNG_MITTY = the reference's exact MT19937 stream

@@ -5,7 +5,9 @@ BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; a
 depth track, block sums and histograms, host BAM reader; additive --device), all five with the additive --gpu-inflate
 (the reader's BGZF blocks inflated on the --device GPU instead of on the host threads), filter-variants
 (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
---rng {mitty,philox}, --corrupt-seed (fused Philox corruption); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
+--rng {mitty,philox}, --corrupt-seed (fused Philox corruption), --gc-bias CURVE / --gc-seed (the sampled templates
+thinned on the GPU by the GC content of the haplotype bytes they span; CURVE from the new gc-bias-model command, which
+fits it to a gc-cov result: the reference has neither); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
 RCCL); the output files are identical to the one-GPU run.  Out of scope for this build (not on the
 generate-reads path): filter-bam (a stub in the reference), describe-read-model (plotting only).
@@ -137,11 +139,20 @@ def print_qname(ctx, param, value):
 @click.option('--rng', type=click.Choice(['mitty', 'philox']), default='mitty',
               help='mitty: bit-exact with the reference; philox: counter-based fast mode')
 @click.option('--corrupt-seed', type=int, default=None, help='Apply the BQ corruption model while writing')
+@click.option('--gc-bias', type=click.Path(), default=None,
+              help='Thin the sampled templates by GC content: a curve file made by gc-bias-model (additive option)')
+@click.option('--gc-seed', type=int, default=None, help='Seed of the GC-bias draws (default: SEED)')
 def generate_reads(fasta, vcf, sample_name, bed, modelfile, coverage, seed, fastq1, fastq2, threads, device, rng,
-                   corrupt_seed):
+                   corrupt_seed, gc_bias, gc_seed):
   """Generate simulated reads"""
   from mitty_amd.readmodel import get_read_model
   from mitty_amd.simulation import readgenerate
+  if gc_bias is not None:   # (a malformed curve fails here, before any input is parsed or a device touched)
+    from mitty_amd.simulation import gcbias
+    try:
+      gc_bias = gcbias.load_curve(gc_bias)
+    except ValueError as e:
+      raise click.BadParameter(str(e), param_hint='--gc-bias')
   read_module, model = get_read_model(modelfile)
   if int(os.environ.get('WORLD_SIZE', '1')) > 1:
     import torch
@@ -151,15 +162,40 @@ def generate_reads(fasta, vcf, sample_name, bed, modelfile, coverage, seed, fast
     dist.init_process_group('nccl')
     try:
       stats = distributed.generate_reads_distributed(fasta, vcf, sample_name, bed, read_module, model, coverage,
-                                                     fastq1, fastq2, seed=seed, rng=rng, corrupt_seed=corrupt_seed)
+                                                     fastq1, fastq2, seed=seed, rng=rng, corrupt_seed=corrupt_seed,
+                                                     gc_bias=gc_bias, gc_seed=gc_seed)
     finally:
       dist.destroy_process_group()
     logging.info('generate-reads: {}'.format(stats))
     return
   stats = readgenerate.process_multi_threaded(fasta, vcf, sample_name, bed, read_module, model, coverage, fastq1,
                                               fastq2, threads=threads, seed=seed, device=device, rng=rng,
-                                              corrupt_seed=corrupt_seed)
+                                              corrupt_seed=corrupt_seed, gc_bias=gc_bias, gc_seed=gc_seed)
   logging.info('generate-reads: {}'.format(stats))
+
+
+@cli.command('gc-bias-model', short_help='Create a GC-bias curve from a gc-cov result')
+@click.argument('gccov_pkl', type=click.Path(exists=True))
+@click.argument('curve_json', type=click.Path())
+@click.option('--min-blocks', type=int, default=20, help='A GC bin with fewer blocks takes its nearest neighbour\'s mean')
+@click.option('--smooth', type=int, default=5, help='Width (odd) of the moving average over the bins')
+@click.option('--desc', default='', help='Description stored in the curve file')
+def gc_bias_model(gccov_pkl, curve_json, min_blocks, smooth, desc):
+  """Turn the pickle written by gc-cov into a GC-bias curve for generate-reads --gc-bias: the mean coverage per
+  GC percent, smoothed and scaled to a maximum of 1.
+
+  GCCOV_PKL is unpickled as it is: it is trusted input, so only give this command a file you made with gc-cov."""
+  import pickle
+  from mitty_amd.simulation import gcbias
+  with open(gccov_pkl, 'rb') as fp:
+    gc_cov = pickle.load(fp)
+  try:
+    if not isinstance(gc_cov, dict) or 'seq_info' not in gc_cov:
+      raise ValueError('{} is not a gc-cov result (no seq_info)'.format(gccov_pkl))
+    w = gcbias.fit_curve(gc_cov, min_blocks=min_blocks, smooth=smooth)
+  except ValueError as e:
+    raise click.ClickException(str(e))
+  gcbias.save_curve(curve_json, w, desc)
 
 
 @cli.command('corrupt-reads', short_help='Apply corruption model to FASTQ file of reads')

@@ -507,6 +507,8 @@ int32_t mh_destroy(mh_ctx *ctx) {
     if (kv.second.used) (void)hipEventDestroy(kv.second.used);
   }
   release(ctx->jump_polys); release(ctx->perm_tmp); release(ctx->nrun_tmp); release(ctx->dec_buf);
+  release(ctx->gc_buf);
+  for (auto &b : ctx->gc_out) release(b);
   for (auto &b : ctx->pb) release(b);
   release(ctx->pb_tmp);
   release(ctx->gz_slots); release(ctx->gz_tok); release(ctx->gz_info); release(ctx->gz_off); release(ctx->gz_scan); release(ctx->gz_out);

@@ -29,6 +29,7 @@
 #include <climits>
 #include <cstring>
 
+#include "mh_device.h"
 #include "mh_internal.h"
 #include "mh_scan.h"
 
@@ -207,13 +208,6 @@ __global__ void __launch_bounds__(256) k_cov_covered(const int32_t *depth, const
   }
 }
 
-// bytes of w equal to c, exactly (no carry between bytes)
-__device__ __forceinline__ int cv_count_eq(uint32_t w, uint32_t c) {
-  const uint32_t x = w ^ (c * 0x01010101u);
-  const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);   // 0x80 where the byte of x is 0
-  return __popc(t);
-}
-
 // block k: the disjoint [k bl, min((k + 1) bl, LN)) and the one base at (k + 1) bl it shares with block k + 1
 __global__ void __launch_bounds__(256) k_cov_gc(const uint8_t *seq, int64_t ln, int64_t bl, int64_t nb, uint32_t *n_n,
                                                 uint32_t *n_gc) {
@@ -229,8 +223,8 @@ __global__ void __launch_bounds__(256) k_cov_gc(const uint8_t *seq, int64_t ln, 
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          nn += cv_count_eq(w[i], 'N');
-          ngc += cv_count_eq(w[i], 'G') + cv_count_eq(w[i], 'C');
+          nn += count_eq4(w[i], 'N');
+          ngc += count_eq4(w[i], 'G') + count_eq4(w[i], 'C');
         }
       } else {
         for (int64_t x = max(lo, s); x < min(lo + 16, e); x++) {

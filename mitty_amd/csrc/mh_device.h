@@ -19,6 +19,13 @@ __device__ __forceinline__ uint32_t byte_eq(uint32_t x, uint32_t c) {
   return (t >> 7) * 0xffu;
 }
 
+// bytes of w equal to c, exactly (no carry between bytes)
+__device__ __forceinline__ int count_eq4(uint32_t w, uint32_t c) {
+  const uint32_t x = w ^ (c * 0x01010101u);
+  const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);   // 0x80 where the byte of x is 0
+  return __popc(t);
+}
+
 // str.maketrans('ATCGN', 'TAGCN') on four bytes at once ('A'^'T' = 0x15, 'C'^'G' = 0x04; others unchanged)
 __device__ __forceinline__ uint32_t comp4(uint32_t x) {
   const uint32_t at = byte_eq(x, 0x41414141u) | byte_eq(x, 0x54545454u);

@@ -444,6 +444,11 @@ struct mh_ctx {
   mh::ModelState model{mh::MODEL_TEXTS}, bq{mh::BQ_TEXTS};
   // gc-cov session
   mh::CovState cov;
+  // GC-bias thinning (mh_gc_thin): bin counts, kept total, thresholds, then a keep flag per template; and the arrays
+  // (fo0, pos0, pos1, n0) the next thinned set is compacted into, swapped with the set's own, which no writer reads
+  // then, so a steady run allocates and frees nothing per unit
+  mh::DevBuf gc_buf;
+  mh::DevBuf gc_out[4];
 };
 
 namespace mh {

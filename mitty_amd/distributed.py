@@ -129,13 +129,22 @@ class DeviceBackend:
     import numpy as np
     self.eng.ctx.set_corruption(True, model['cum_bq_mat'], 10 ** (-np.arange(100) / 10), seed)
 
+  def set_gc_bias(self, weight, seed):
+    """Every set sample() makes is thinned by the GC-bias curve `weight` (Engine.set_gc_bias) before it is counted,
+    shared or sliced: a template's draw is keyed by its index in the whole sampled set."""
+    self.eng.set_gc_bias(weight, seed)
+
+  def gc_counts(self):
+    """(seen[101], kept[101]) of the sets this rank sampled and thinned."""
+    return list(self.eng.gc_seen), list(self.eng.gc_kept)
+
   def load_region(self, ri, region, seq):
     self.eng.load_region(ri, region, seq)
 
   def sample(self, units, soa_of, p, rlen, cum_tlen, rng, which=None, ids=None):
     """units: [(ps, ri, cpy, seed)]; the units k in `which` (all by default) are sampled into template set ids[k]
     (k by default).  Every unit's haplotype is built (its slices are emitted here).  Returns template counts (None
-    where not sampled)."""
+    where not sampled); with a GC-bias curve set, the counts of the thinned sets."""
     from mitty_amd.engine import RNG_MODES
     ids = list(range(len(units))) if ids is None else list(ids)
     for k, (_, ri, cpy, _) in enumerate(units):
@@ -147,6 +156,10 @@ class DeviceBackend:
                                      [units[k][3] for k in which], p, rlen, cum_tlen, RNG_MODES[rng])
       for k, n in zip(which, ns):
         out[k] = int(n)
+      if self.eng._gc is not None:
+        for k in which:
+          self.eng._gc_thin(ids[k], self._slots[ids[k]], units[k][3])
+          out[k] = self.eng.ctx.template_count(ids[k])
     return out
 
   # the broadcast buffer of a template set of n templates: pos0 at 0, pos1 at 8n, fo0 at 16n (17 B per template)
@@ -273,7 +286,8 @@ class DeviceBackend:
 def generate_reads_distributed(fasta_fname, vcf_fname, sample_name, bed_fname, read_module, model, coverage,
                                fastq1_fname, fastq2_fname, seed=7, rng='mitty', corrupt_seed=None, backend=None,
                                group=None, max_batch_draws=200_000_000, layout=None, bam_fname=None,
-                               bam_header_text=None, bam_refs=None, bam_capacity=0, bam_spill_dir=None):
+                               bam_header_text=None, bam_refs=None, bam_capacity=0, bam_spill_dir=None, gc_bias=None,
+                               gc_seed=None):
   """process_multi_threaded (readgenerate.py:76-126) over the ranks of the default process group.
 
   `backend` defaults to DeviceBackend(LOCAL_RANK); tests pass a host stand-in to exercise the orchestration with
@@ -281,10 +295,19 @@ def generate_reads_distributed(fasta_fname, vcf_fname, sample_name, bed_fname, r
   bam_fname: also the god-aligner's BAM (+ .bai) of the reads, header bam_header_text, @SQ bam_refs [(name, length)]
   (god_aligner.construct_header from the FASTA's .ann); bam_capacity: each rank's range store's record bytes in HBM
   before a spill; bam_spill_dir: spill to unlinked temporary files there instead of host memory.
+  gc_bias / gc_seed: as process_multi_threaded's.  Each set is thinned on the rank that samples it, right after
+  sampling, so every count that is all-reduced and every array that is broadcast is already thinned; the stats gain
+  this rank's gc_seen / gc_kept and their per-bin lists.
   """
   import torch.distributed as dist
   from mitty_amd.simulation.readgenerate import get_data_for_workers
   t0 = time.time()
+  if gc_bias is not None:
+    from mitty_amd.simulation import gcbias
+    gc_bias = gcbias.check_weight(gc_bias)
+    if backend is not None and not hasattr(backend, 'set_gc_bias'):
+      raise NotImplementedError('gc_bias: backend {} has no set_gc_bias (the thinning runs on the device)'.format(
+        type(backend).__name__))
   rank = dist.get_rank(group) if dist.is_initialized() else 0
   world = dist.get_world_size(group) if dist.is_initialized() else 1
   read_model = read_module.read_model_params(model, coverage)
@@ -301,6 +324,8 @@ def generate_reads_distributed(fasta_fname, vcf_fname, sample_name, bed_fname, r
     backend = DeviceBackend(int(os.environ.get('LOCAL_RANK', '0')))
   if corrupt_seed is not None:
     backend.set_corruption(model, corrupt_seed)
+  if gc_bias is not None:
+    backend.set_gc_bias(gc_bias, seed if gc_seed is None else gc_seed)
   regions = sorted({units[u][1] for u in my_units})
   if regions:
     seqs = mfasta.read_fasta(fasta_fname, names={vdf[ri]['region'][0] for ri in regions})
@@ -451,6 +476,9 @@ def generate_reads_distributed(fasta_fname, vcf_fname, sample_name, bed_fname, r
   held.clear()
   if bam_fname is not None:
     stats['bam_records'] = _bam_write_ranges(backend, rank, world, group, bam_fname, bam_header_text, bam_refs)
+  if gc_bias is not None:
+    stats['gc_bin_seen'], stats['gc_bin_kept'] = backend.gc_counts()
+    stats['gc_seen'], stats['gc_kept'] = sum(stats['gc_bin_seen']), sum(stats['gc_bin_kept'])
   tot = allreduce_i64([stats['templates'], stats['kept']] + raw, group)
   if world > 1:
     dist.barrier(group)

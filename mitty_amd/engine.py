@@ -38,6 +38,21 @@ class Engine:
     self._tpl_base = 0
     self._lazy_n = []    # template counts of the units queued by run_units and not yet collected
     self._two_pass_done = []
+    self._gc = None      # (thresholds uint64[101], seed) of set_gc_bias
+    self.gc_seen = [0] * _native.GC_BINS   # templates seen / kept per GC bin by the thinning so far
+    self.gc_kept = [0] * _native.GC_BINS
+
+  def set_gc_bias(self, weight, seed):
+    """Thin every unit's sampled templates by GC content before emission (mh_gc_thin): weight = the curve's 101
+    weights (simulation.gcbias), or None for no thinning; seed keys the draws with the unit's own seed."""
+    from mitty_amd.simulation import gcbias
+    self._gc = None if weight is None else (gcbias.thresholds(weight), int(seed))
+
+  def _gc_thin(self, tpl_id, slot, unit_seed):
+    _, seen, kept = self.ctx.gc_thin(tpl_id, slot, self._gc[0], self._gc[1], unit_seed)
+    for b in range(_native.GC_BINS):
+      self.gc_seen[b] += int(seen[b])
+      self.gc_kept[b] += int(kept[b])
 
   def close(self):
     self.ctx.close()
@@ -150,6 +165,8 @@ class Engine:
     if prefetch and prefetch_after < 0:   # (before unit 0: beside this batch's sampling head)
       self.prefetch(prefetch, prefetch_next_step, p, rng)
     for k, (ps, ri, cpy, seed) in enumerate(units):
+      if self._gc is not None:
+        self._gc_thin(base + k, slots[k], seed)
       self.ctx.use_templates(base + k)
       self.ctx.emit_async(slots[k], '{}:{}:{}'.format(sample_name, worker_id, ps), self._regions[ri][0], cpy,
                           write_fastq2, unit_key=seed)
@@ -175,6 +192,8 @@ class Engine:
                                             for c0 in range(k0, len(units), self.EMIT_SETS)]
     for chunk in chunks:
       for k, (ps, ri, cpy, seed) in chunk:
+        if self._gc is not None:
+          self._gc_thin(base + k, slots[k], seed)
         self.ctx.use_templates(base + k)
         self.ctx.emit_prepare(slots[k], '{}:{}:{}'.format(sample_name, worker_id, ps), self._regions[ri][0], cpy,
                               write_fastq2, unit_key=seed, wait=False)

@@ -69,7 +69,7 @@ def get_data_for_workers(model, vcf, seed):
 def process_multi_threaded(fasta_fname, vcf_fname, sample_name, bed_fname, read_module, model, coverage,
                            fastq1_fname, fastq2_fname, threads=2, seed=7, device=0, rng='mitty', corrupt_seed=None,
                            flush_bytes=1 << 30, max_batch_units=32, max_batch_draws=200_000_000, compress=None,
-                           gz_level=6, gz_threads=8, gz_device=True, stage_times=False):
+                           gz_level=6, gz_threads=8, gz_device=True, stage_times=False, gc_bias=None, gc_seed=None):
   """Generate reads for every (region, copy, pass) unit and write FASTQ (reference readgenerate.py:76-126).
 
   compress: None = BGZF for file names ending in '.gz' (FastqSink), True / False forces it; gz_device: deflated on
@@ -78,8 +78,14 @@ def process_multi_threaded(fasta_fname, vcf_fname, sample_name, bed_fname, read_
   = gpu_s + flush_s, flush_s = fetch_s (waiting for the GPU and its D2H, deflate included) + write_s (waiting for
   the file writes to free a staging slot) + bookkeeping, close_s = files closed and the engine released).
   stage_times: also the device's per-stage times (stages_ms: e.g. bgzf_deflate, bgzf_d2h, output_d2h, emit).
+  gc_bias: a GC-bias curve (101 weights, simulation.gcbias) every unit's sampled templates are thinned by on the
+  device before emission, keyed by gc_seed (default: seed); `templates` then counts the thinned sets, and the stats
+  gain gc_seen / gc_kept (templates before / after thinning) and their per-bin lists gc_bin_seen / gc_bin_kept.
   """
   t0 = time.time()
+  if gc_bias is not None:
+    from mitty_amd.simulation import gcbias
+    gc_bias = gcbias.check_weight(gc_bias)   # (before a device is touched)
   read_model = read_module.read_model_params(model, coverage)
   vdf = vcfio.load_variants_soa(vcf_fname, sample_name, bed_fname)
   seqs = mfasta.read_fasta(fasta_fname, names={r['region'][0] for r in vdf})
@@ -92,6 +98,8 @@ def process_multi_threaded(fasta_fname, vcf_fname, sample_name, bed_fname, read_
   if corrupt_seed is not None:
     import numpy as np
     eng.ctx.set_corruption(True, model['cum_bq_mat'], 10 ** (-np.arange(100) / 10), corrupt_seed)
+  if gc_bias is not None:
+    eng.set_gc_bias(gc_bias, seed if gc_seed is None else gc_seed)
   for ri, reg in enumerate(vdf):
     chrom, s0, e = reg['region']
     eng.load_region(ri, reg['region'], mfasta.fetch(seqs, chrom, s0, e))
@@ -193,6 +201,10 @@ def process_multi_threaded(fasta_fname, vcf_fname, sample_name, bed_fname, read_
     # sees them
     stats['run_s'] = time.time() - t_run
     stats['gpu_s'] = stats['run_s'] - stats['flush_s']
+    if gc_bias is not None:
+      stats['gc_bin_seen'], stats['gc_bin_kept'] = list(eng.gc_seen), list(eng.gc_kept)
+      stats['gc_seen'], stats['gc_kept'] = sum(eng.gc_seen), sum(eng.gc_kept)
+      logger.info('gc-bias: {} of {} sampled templates kept'.format(stats['gc_kept'], stats['gc_seen']))
     if stage_times:
       agg = {}
       for name, ms in eng.ctx.stage_times():
