@@ -496,8 +496,6 @@ int32_t mh_destroy(mh_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
   if (ctx->pstream) (void)hipStreamSynchronize(ctx->pstream);
-  for (auto x : ctx->xstream)
-    if (x) (void)hipStreamSynchronize(x);
   for (auto &kv : ctx->contigs) release(kv.second.seq);
   for (auto &kv : ctx->haps) release_hap(kv.second);
   for (auto &h : ctx->hap_spare) release_hap(h);
@@ -515,9 +513,6 @@ int32_t mh_destroy(mh_ctx *ctx) {
   release(ctx->gz_in);
   for (auto &b : ctx->s) release(b);
   for (auto &b : ctx->lane2) release(b);
-  for (auto &l : ctx->xlane)
-    for (auto &b : l) release(b);
-  for (auto &b : ctx->xscan) release(b);
   release(ctx->scan_partials); release(ctx->scan_partials2); release(ctx->d_small);
   release(ctx->corrupt_cum); release(ctx->corrupt_phred);
   release(ctx->out1); release(ctx->out2);
@@ -555,10 +550,6 @@ int32_t mh_destroy(mh_ctx *ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->ev_prefetch) (void)hipEventDestroy(ctx->ev_prefetch);
   if (ctx->pstream) (void)hipStreamDestroy(ctx->pstream);
-  for (int l = 0; l < 2; l++) {
-    if (ctx->xstream[l]) (void)hipStreamDestroy(ctx->xstream[l]);
-    if (ctx->ev_xjoin[l]) (void)hipEventDestroy(ctx->ev_xjoin[l]);
-  }
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return MH_OK;

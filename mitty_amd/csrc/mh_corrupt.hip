@@ -289,7 +289,7 @@ int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_
   if (d1 && n1 / 4 < T) T = n1 / 4;
   if (T == 0) return MH_OK;
   MH_TRY(ensure(ctx, B.tpl, sizeof(CrTpl) * T));
-  MH_TRY(ensure(ctx, ctx->s[13], sizeof(Off3) * (T + 1)));
+  MH_TRY(ensure(ctx, ctx->s[mh_ctx::S_CR_OFF], sizeof(Off3) * (T + 1)));
   MH_TRY(ensure(ctx, ctx->scan_partials, sizeof(Off3) * scan_partials_count(T + 1) + 64));
   MH_TRY(ensure(ctx, ctx->d_small, 8192 + 256));
   int32_t *err = (int32_t *)((char *)ctx->d_small.p + 64);
@@ -299,7 +299,7 @@ int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_
   hipLaunchKernelGGL(k_cr_measure, dim3(grid_for(T, 256, INT32_MAX)), dim3(256), 0, st, d0, (const int64_t *)B.nl1.p,
                      d1, d1 ? (const int64_t *)B.nl2.p : nullptr, nf, T, ctx->corrupt_max_bp, tpl, err);
   HIPCHK(ctx, hipGetLastError());
-  Off3 *off = (Off3 *)ctx->s[13].p;
+  Off3 *off = (Off3 *)ctx->s[mh_ctx::S_CR_OFF].p;
   HIPCHK(ctx, device_scan<Off3>(st, T + 1, LoadCr{tpl, T}, StoreCr{off}, OpSum{}, Off3{0, 0, 0},
                                 (Off3 *)ctx->scan_partials.p, (Off3 *)((char *)ctx->d_small.p + 128)));
   stage_end(ctx);

@@ -348,16 +348,31 @@ struct mh_ctx {
   mh::DevBuf dec_buf;   // chunk-parallel shuffle decode: chunk jobs, starts, counts, work list
   int64_t dec_passes = 0;   // count passes of the last chunk-parallel decode (diagnostics)
 
-  // scratch (grow-only), reused by all stages
+  // scratch (grow-only), reused by all stages: one array, its buffers named by use.  Names with the same number are
+  // one buffer, on purpose (the peak allocation counts every buffer once); each pair is safe for the reason given.
+  enum : int {
+    S_WORDS = 0,      // the batch's MT19937 / Philox words, every unit's four streams
+    S_UNIT = 1,       // per unit: templates kept, decode status, geometric flag count
+    S_JOBS = 2,       // the batch's SegJob and DecJob tables
+    S_J = 3,          // the batch's shuffle swap indices
+    // sampling lane 0 (SampleLane, mh_sample.hip); lane 1 has the same seven, in the same order, in lane2[0..6]
+    S_TS = 4, S_TS_SHUF = 5, S_TE = 6, S_KEEP = 7, S_SORT_KEYS = 8, S_SORT_VALS = 9, S_HEADS = 10,
+    S_FLAG_IDX = 11,  // indices of the geometric draws flagged for the host (GeoFlags)
+    // the exact path's draws of the unit being redone (unit_fixup), and the batch permutation's unit offsets and
+    // counts (k_perm_keys): the main stream runs k_perm_keys in the batch's head, before any of its fix-ups
+    S_EXACT_DRAWS = 12, S_UNIT_SPANS = 12,
+    // the cumulative template length table of the batch, and corrupt_fastq's record offsets: corrupt_fastq is its
+    // own entry point, which first resolves a pending asynchronous tail (the table's last reader) and runs on the
+    // main stream
+    S_CUM_TLEN = 13, S_CR_OFF = 13,
+    // the splice's first-lane scratch (splice_build: anchors, accepted, ref_before, node sources) on sampling lane
+    // 0's te, keep and sort buffers: both run on the main stream, each done with them before the other starts
+    S_SPL_ANCHOR = 6, S_SPL_ACC = 7, S_SPL_REFB = 8, S_SPL_NSRC = 9,
+  };
   mh::DevBuf s[16];
   mh::DevBuf scan_partials;
-  mh::DevBuf lane2[8];   // the second lane's copies of s[4..10] and its radix-sort scratch (index 7)
+  mh::DevBuf lane2[8];   // the second lane's copies of s[S_TS..S_HEADS] and its radix-sort scratch (index 7)
   mh::DevBuf scan_partials2;
-  // lanes 2 and 3 (a four-unit job's units each on a lane of their own): streams, scratch, join events
-  hipStream_t xstream[2] = {nullptr, nullptr};
-  mh::DevBuf xlane[2][8];
-  mh::DevBuf xscan[2];
-  hipEvent_t ev_xjoin[2] = {nullptr, nullptr};
   mh::DevBuf sl2[8];   // the splice's second lane: anchor, accepted, ref_before, node src, small, partials, N runs, sort
   // mh_prefetch_haplotypes_vset: the next batch's splices issued by a host thread of the context on a stream of their
   // own (the fourth: GPU_MAX_HW_QUEUES is 4) with their own scratch and pinned readback block

@@ -43,8 +43,7 @@ void jump_poly_words(uint64_t L, int64_t k, uint32_t *out624);
 namespace {
 
 constexpr uint32_t MT_UP = 0x80000000u, MT_LO = 0x7fffffffu, MT_A = 0x9908b0dfu;
-constexpr int64_t SEG_WORDS_DEFAULT = 624 * 640;   // outputs per segment (twice as long: within noise, round 5)
-static int64_t seg_words() { return SEG_WORDS_DEFAULT; }
+constexpr int64_t SEG_WORDS = 624 * 640;   // outputs per segment (twice as long: within noise, round 5)
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
   y ^= (y >> 11);
@@ -1009,7 +1008,7 @@ __global__ void __launch_bounds__(256) k_mt_state(const uint32_t *key, int32_t p
 
 int32_t mt_stream_words(mh_ctx *ctx, hipStream_t st, uint32_t seed, int64_t first, int64_t count, DevBuf &out,
                         DevBuf &jobs_buf, int64_t *lead) {
-  const int64_t SEG = seg_words();
+  const int64_t SEG = SEG_WORDS;
   const int64_t k0 = first / SEG, k1 = (first + std::max<int64_t>(count, 1) - 1) / SEG;
   *lead = first - k0 * SEG;
   MH_TRY(ensure(ctx, out, 4 * (size_t)((k1 - k0 + 1) * SEG) + 64));
@@ -1050,28 +1049,32 @@ struct UnitPlan {
   TplSet *out;
 };
 
-// Chunk-parallel Fisher-Yates decode of every unit in `dec` (see k_decode_chunks).  On success the swap indices are
-// written and d_status[u] = draws left undecoded (0 unless the unit ran out of pre-generated words); *done = false
-// when the starts did not reach their fixed point within the pass budget (the caller then runs k_shuffle_decode2).
-int32_t decode_parallel(mh_ctx *ctx, const std::vector<DecJob> &dec, int64_t *d_status, bool *done) {
-  hipStream_t st = ctx->stream;
-  *done = false;
+// The host-side plan of the chunk-parallel decode: every unit's word stream cut into chunks with their expected
+// starts, each unit's tail, and the tiles of chunks k_decode_resolve walks.
+struct DecPlan {
+  std::vector<ChunkJob> cj;
+  std::vector<int64_t> s0;        // per chunk: the draw index it is expected to start at
+  std::vector<int32_t> first;     // per unit (+ 1): its first chunk
+  std::vector<int32_t> tail_c;    // per unit: the first chunk of its tail, or -1
+  std::vector<DecTile> tiles;
+};
+
+DecPlan plan_decode(const std::vector<DecJob> &dec) {
+  DecPlan P;
   // Chunks shrink with the draw index: a chunk's margin (in draws) is about mask(i) / its words, so sizing chunks as
   // i / 128 words (a power of two, 64 .. DC_CHUNK) keeps margins from collapsing as i falls.
   // Starts: the exact one for each unit's first chunk, then the expected accepts (rate (i+1)/(mask+1)).
   const int64_t div = 128;
   const int64_t minw = 64;
-  std::vector<ChunkJob> cj;
-  std::vector<int64_t> s0;
-  std::vector<int32_t> first(dec.size() + 1, 0);
+  P.first.assign(dec.size() + 1, 0);
   for (size_t u = 0; u < dec.size(); u++) {
-    first[u] = (int32_t)cj.size();
+    P.first[u] = (int32_t)P.cj.size();
     double i = (double)(dec[u].n - 1);
     for (int64_t b = 0; b < dec[u].n_words;) {
       int64_t size = DC_CHUNK;
       while (size > minw && (double)size * (double)div > i) size >>= 1;
-      cj.push_back(ChunkJob{dec[u].words, dec[u].n_words, b, dec[u].j, 0, (int32_t)size});
-      s0.push_back(b == 0 ? dec[u].n - 1 : (i >= 1.0 ? (int64_t)llround(i) : 0));
+      P.cj.push_back(ChunkJob{dec[u].words, dec[u].n_words, b, dec[u].j, 0, (int32_t)size});
+      P.s0.push_back(b == 0 ? dec[u].n - 1 : (i >= 1.0 ? (int64_t)llround(i) : 0));
       double rem = (double)size;
       while (rem > 0 && i >= 1.0) {   // integrate the acceptance rate piecewise over mask epochs
         uint32_t ii = (uint32_t)i, m = ii;
@@ -1085,46 +1088,83 @@ int32_t decode_parallel(mh_ctx *ctx, const std::vector<DecJob> &dec, int64_t *d_
       b += size;
     }
   }
-  first[dec.size()] = (int32_t)cj.size();
+  P.first[dec.size()] = (int32_t)P.cj.size();
+  const int32_t U = (int32_t)dec.size();
+  // the tail of each unit: its chunks from the first one expected to start below 2^15 draws
+  const int64_t tail_at = (int64_t)1 << 15;
+  P.tail_c.assign(U, -1);
+  for (int32_t u = 0; u < U; u++)
+    for (int32_t c = P.first[u]; c < P.first[u + 1]; c++)
+      if (P.s0[c] < tail_at) {
+        P.tail_c[u] = c;
+        for (int32_t k = c; k < P.first[u + 1]; k++) P.cj[k].tail = 1;
+        break;
+      }
+  for (int32_t u = 0; u < U; u++) {
+    const int32_t ft = (int32_t)P.tiles.size();
+    for (int32_t b = P.first[u]; b < P.first[u + 1]; b += DR_TILE)
+      P.tiles.push_back(DecTile{u, b, std::min(b + DR_TILE, P.first[u + 1]), ft});
+  }
+  return P;
+}
+
+// dec_buf's layout for C chunks, U units and T tiles: byte offsets of its arrays and the size to reserve.  The one
+// place that says either.
+struct DecLayout {
+  size_t jobs, s0, s1, ndraw, rem, tail, tiles, count, todo, margin, ntodo, bytes;
+};
+
+DecLayout dec_layout(size_t C, size_t U, size_t T) {
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = at;
+    at += bytes;
+    return o;
+  };
+  DecLayout L;
+  L.jobs = take(((sizeof(ChunkJob) * C + 15) / 16) * 16);
+  L.s0 = take(8 * C);
+  L.s1 = take(8 * C);
+  L.ndraw = take(8 * U);
+  L.rem = take(8 * U);
+  L.tail = take(sizeof(TailJob) * U);
+  L.tiles = take(sizeof(DecTile) * (T + 1));
+  L.count = take(4 * C);
+  L.todo = take(4 * C);
+  L.margin = take(4 * 2 * C);
+  L.ntodo = take(512);   // two queue counters, alternating by pass, and slack
+  L.bytes = at;
+  return L;
+}
+
+// Chunk-parallel Fisher-Yates decode of every unit in `dec` (see k_decode_chunks).  On success the swap indices are
+// written and d_status[u] = draws left undecoded (0 unless the unit ran out of pre-generated words); *done = false
+// when the starts did not reach their fixed point within the pass budget (the caller then runs k_shuffle_decode2).
+int32_t decode_parallel(mh_ctx *ctx, const std::vector<DecJob> &dec, int64_t *d_status, bool *done) {
+  hipStream_t st = ctx->stream;
+  *done = false;
+  const DecPlan P = plan_decode(dec);
+  const std::vector<ChunkJob> &cj = P.cj;
+  const std::vector<int64_t> &s0 = P.s0;
+  const std::vector<int32_t> &tail_c = P.tail_c;
+  const std::vector<DecTile> &tiles = P.tiles;
   const int64_t C = (int64_t)cj.size();
   if (C == 0) {
     *done = true;
     return MH_OK;
   }
   const int32_t U = (int32_t)dec.size();
-  // the tail of each unit: its chunks from the first one expected to start below 2^15 draws
-  const int64_t tail_at = (int64_t)1 << 15;
-  std::vector<int32_t> tail_c(U, -1);
-  for (int32_t u = 0; u < U; u++)
-    for (int32_t c = first[u]; c < first[u + 1] && tail_at > 0; c++)
-      if (s0[c] < tail_at) {
-        tail_c[u] = c;
-        for (int32_t k = c; k < first[u + 1]; k++) cj[k].tail = 1;
-        break;
-      }
-  const int32_t tile_sz = DR_TILE;
-  std::vector<DecTile> tiles;
-  for (int32_t u = 0; u < U; u++) {
-    const int32_t ft = (int32_t)tiles.size();
-    for (int32_t b = first[u]; b < first[u + 1]; b += tile_sz)
-      tiles.push_back(DecTile{u, b, std::min(b + tile_sz, first[u + 1]), ft});
-  }
   const int32_t T = (int32_t)tiles.size();
-  const size_t bytes = ((sizeof(ChunkJob) * C + 15) / 16) * 16 + 8 * C * 2 + 8 * U * 2 + sizeof(TailJob) * U +
-                       sizeof(DecTile) * (T + 1) + 4 * C * 2 + 8 * C + 512;
-  MH_TRY(ensure(ctx, ctx->dec_buf, bytes));
+  const DecLayout L = dec_layout((size_t)C, (size_t)U, (size_t)T);
+  MH_TRY(ensure(ctx, ctx->dec_buf, L.bytes));
   char *p = (char *)ctx->dec_buf.p;
-  ChunkJob *d_jobs = (ChunkJob *)p;
-  int64_t *d_s0 = (int64_t *)(p + ((sizeof(ChunkJob) * C + 15) / 16) * 16);
-  int64_t *d_s1 = d_s0 + C;
-  int64_t *d_ndraw = d_s1 + C;
-  int64_t *d_rem = d_ndraw + U;
-  TailJob *d_tail = (TailJob *)(d_rem + U);
-  DecTile *d_tiles = (DecTile *)(d_tail + U);
-  int32_t *d_count = (int32_t *)(d_tiles + T + 1);
-  int32_t *d_todo = d_count + C;
-  int32_t *d_margin = d_todo + C;
-  int32_t *d_ntodo = d_margin + 2 * C;   // two queue counters, alternating by pass
+  ChunkJob *d_jobs = (ChunkJob *)(p + L.jobs);
+  int64_t *d_s0 = (int64_t *)(p + L.s0), *d_s1 = (int64_t *)(p + L.s1);
+  int64_t *d_ndraw = (int64_t *)(p + L.ndraw), *d_rem = (int64_t *)(p + L.rem);
+  TailJob *d_tail = (TailJob *)(p + L.tail);
+  DecTile *d_tiles = (DecTile *)(p + L.tiles);
+  int32_t *d_count = (int32_t *)(p + L.count), *d_todo = (int32_t *)(p + L.todo);
+  int32_t *d_margin = (int32_t *)(p + L.margin), *d_ntodo = (int32_t *)(p + L.ntodo);
   std::vector<int64_t> ndraw(U);
   for (int32_t u = 0; u < U; u++) ndraw[u] = dec[u].n;
   std::vector<TailJob> tj;
@@ -1196,159 +1236,238 @@ int32_t decode_parallel(mh_ctx *ctx, const std::vector<DecJob> &dec, int64_t *d_
   return MH_OK;
 }
 
-// Everything after the word streams for one unit: ts (geometric scan), shuffle, tlen + keep + compaction into
-// `out`, file order.  `exact`: materialise the draws and recompute flagged ones on the host (rare path).
-// `lane` 1 runs on the second sampling stream with its own scratch (the units' stages are latency-bound, so two
-// units side by side fill the chip better than one after the other).
-// phase: 0 = everything; 1 = the geometric scan (and a per-unit sort); 2 = the rest.
-// bp (the batch-wide permutation): phase 1 writes the unit's ts into bp_ts + j_off, phase 2 takes its shuffled ts
-// from bp_tsh + j_off; the unit's own sort and chase are skipped
-// The permutation's (target, step) sort: the hand-written LSD radix sort of mh_sort.h (9-bit digits with the tile
-// counts folded into the scatter: a 64 M-draw batch's 27-bit keys in 3 passes, 512-thread workgroups that fit beside
-// the FASTQ writers; round 5's A/B against rocprim's onesweep: within noise).
-template <class KIn>
-static hipError_t perm_sort(void *tmp, size_t &tmp_bytes, KIn keys_in, uint32_t *keys_out, uint32_t *vals_out,
-                            size_t n, unsigned end_bit, hipStream_t st) {
-  return lsd_sort_pairs_iota(tmp, tmp_bytes, keys_in, keys_out, vals_out, (int64_t)n, end_bit, st);
-}
-
 struct BatchPerm {
   int64_t *ts, *tsh;
 };
 
-int32_t finish_unit(mh_ctx *ctx, UnitPlan &u, const uint32_t *words, const uint32_t *jarr, double p, int32_t rlen,
-                    const double *d_cum, int32_t n_tlen, int32_t rng_mode, bool exact, int64_t *d_m,
-                    uint32_t *d_flag, int lane = 0, int phase = 0, const BatchPerm *bp = nullptr) {
-  hipStream_t st = lane == 0 ? ctx->stream : lane == 1 ? ctx->stream2 : ctx->xstream[lane - 2];
-  ctx->stage_stream = lane ? st : nullptr;
-  struct Restore {
-    mh_ctx *c;
-    ~Restore() { c->stage_stream = nullptr; }
-  } restore{ctx};
-  mh::DevBuf *S4 = lane == 0 ? ctx->s + 4 : lane == 1 ? ctx->lane2 : ctx->xlane[lane - 2];   // the lane's s[4..10]
-  mh::DevBuf &perm_tmp = lane == 0 ? ctx->perm_tmp : S4[7];
-  void *scan_partials = lane == 0 ? ctx->scan_partials.p : lane == 1 ? ctx->scan_partials2.p : ctx->xscan[lane - 2].p;
-  const int64_t n = u.n;
-  const uint32_t *w_tloc = words + u.w_tloc, *w_tlen = words + u.w_tlen, *w_fo = words + u.w_fo;
-  int64_t *ts = bp ? bp->ts + u.j_off : (int64_t *)S4[0].p;
-  int64_t *ts_shuf = (int64_t *)S4[1].p, *te = (int64_t *)S4[2].p;
-  uint32_t *sk = (uint32_t *)S4[4].p, *sv = (uint32_t *)S4[5].p;
-  int32_t *nxt = (int32_t *)S4[6].p;
-  const bool permute = rng_mode == MH_RNG_MITTY && n > 1 && !bp;
-  uint8_t *keep = (uint8_t *)S4[3].p;
-  int64_t *flag_idx = (int64_t *)ctx->s[11].p;
-  int64_t *tot = (int64_t *)((char *)ctx->d_small.p + 128 + 64 * lane);
-  const double log_q = std::log(1.0 - p);
-  GeoFlags fl{flag_idx, d_flag, 1024};
-
-  if (phase != 2) {
-    stage_begin(ctx, "sample_geometric_scan");
-    if (!exact) {
-      HIPCHK(ctx, device_scan_sum<int64_t>(st, n, LoadGeo{w_tloc, p, log_q, fl}, StoreTs{ts, u.p_min + 1, u.ni},
-                                           scan_partials, tot));
-    } else {
-      int64_t *g = (int64_t *)ctx->s[12].p;
-      uint32_t nflag = 0;
-      HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4, st));
-      hipLaunchKernelGGL(k_geo_array, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, n, w_tloc, p, log_q, fl, g);
-      HIPCHK(ctx, hipMemcpyAsync(&nflag, d_flag, 4, hipMemcpyDeviceToHost, st));
-      SYNCCHK(ctx, hipStreamSynchronize(st));
-      auto host_geo = [&](const uint32_t *ww) {   // numpy legacy_random_geometric_inversion on the host libm
-        double U = (((int32_t)(ww[0] >> 5)) * 67108864.0 + ((int32_t)(ww[1] >> 6))) / 9007199254740992.0;
-        return (int64_t)std::ceil(std::log1p(-U) / std::log(1.0 - p));
-      };
-      if (ctx->force_geo && p < 0.333333333333333333333333) {
-        // MH_DEC_FORCE_GEO (tests): every draw of the unit from the host libm, so this path is pinned against the
-        // oracle on whole units, not only on the rare draws the device flags
-        std::vector<uint32_t> hw(2 * (size_t)n);
-        std::vector<int64_t> hg((size_t)n);
-        HIPCHK(ctx, hipMemcpy(hw.data(), w_tloc, 8 * (size_t)n, hipMemcpyDeviceToHost));
-        for (int64_t k = 0; k < n; k++) hg[k] = host_geo(hw.data() + 2 * k);
-        HIPCHK(ctx, hipMemcpy(g, hg.data(), 8 * (size_t)n, hipMemcpyHostToDevice));
-      } else {
-        if (nflag > 1024) return arg_fail(ctx, MH_E_ARG, "too many near-integer geometric quotients");
-        std::vector<int64_t> idx(nflag);
-        if (nflag) HIPCHK(ctx, hipMemcpy(idx.data(), flag_idx, 8 * nflag, hipMemcpyDeviceToHost));
-        for (int64_t k : idx) {
-          uint32_t ww[2];
-          HIPCHK(ctx, hipMemcpy(ww, w_tloc + 2 * k, 8, hipMemcpyDeviceToHost));
-          int64_t gv = host_geo(ww);   // the reference's libm
-          HIPCHK(ctx, hipMemcpy(g + k, &gv, 8, hipMemcpyHostToDevice));
-        }
-      }
-      HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4, st));
-      HIPCHK(ctx, device_scan<int64_t>(st, n, LoadArr{g}, StoreTs{ts, u.p_min + 1, u.ni}, OpSum{}, (int64_t)0,
-                                       (int64_t *)scan_partials, tot));
-    }
-    stage_end(ctx);
-
-    if (permute) {
-      stage_begin(ctx, "sample_permutation");
-      // steps sorted by (target, step): keys j, values the step index (stable LSD radix sort over the target's bits)
-      unsigned end_bit = 1;
-      while (end_bit < 32 && ((int64_t)1 << end_bit) < n) end_bit++;
-      size_t tmp = 0;
-      HIPCHK(ctx, perm_sort(nullptr, tmp, jarr, sk, sv, (size_t)n, end_bit, st));
-      MH_TRY(ensure(ctx, perm_tmp, tmp + 256));
-      HIPCHK(ctx, perm_sort(perm_tmp.p, tmp, jarr, sk, sv, (size_t)n, end_bit, st));
-      HIPCHK(ctx, hipMemsetAsync(nxt, 0xff, 4 * (size_t)n, st));
-      hipLaunchKernelGGL(k_perm_heads, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, n, (const uint32_t *)sk,
-                         (const uint32_t *)sv, nxt);
-      HIPCHK(ctx, hipGetLastError());
-      stage_end(ctx);
-    }
-  }
-  if (phase == 1) return MH_OK;
-
-  const int64_t *ts_use = bp && rng_mode == MH_RNG_MITTY && n > 1 ? bp->tsh + u.j_off : ts;
-  if (permute) {
-    stage_begin(ctx, "sample_permutation");
-    hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, (int64_t)0, n,
-                       (const uint32_t *)sk, (const uint32_t *)sv, (const int32_t *)nxt, (const int64_t *)ts, ts_shuf);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
-    ts_use = ts_shuf;
-  }
-
-  stage_begin(ctx, "sample_tlen_compact");
-  hipLaunchKernelGGL(k_tlen, dim3(grid_for((n + TLEN_PER - 1) / TLEN_PER, 256, INT32_MAX)), dim3(256), 8 * n_tlen, st,
-                     n, w_tlen, d_cum, n_tlen,
-                     (int64_t)rlen, u.p_max, ts_use, te, keep);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, device_scan_sum<int64_t>(st, n, LoadKeep{keep},
-                                       StoreCompact{keep, ts_use, te, (int64_t *)u.out->pos0.p,
-                                                    (int64_t *)u.out->pos1.p, (int64_t)rlen, w_fo,
-                                                    (int8_t *)u.out->fo0.p,
-                                                    u.out->has_n0 ? (int32_t *)u.out->n0.p : nullptr},
-                                       scan_partials, d_m));
-  stage_end(ctx);
-  return MH_OK;
-}
-
 }  // namespace
 
-// A batch's sampling state between its two halves (sample_head / sample_tail): the plan, the batch buffers and the
-// lanes.  The batch buffers are shared by every batch.
+// A batch's sampling state between its two halves (sample_head / sample_tail): the plan and the batch buffers, which
+// are shared by every batch.
 struct SampleState {
   std::vector<UnitPlan> plan;
   int32_t n_units = 0, rng_mode = 0, rlen = 0, n_tlen = 0, n_lanes = 1;
-  bool two_lanes = false, batch = false;
+  bool batch = false;   // the batch-wide permutation (else every unit runs its own)
   double p = 0;
-  int64_t j_total = 0, nn = 0;
+  int64_t j_total = 0, nn = 0;   // the batch's j entries; the most draws a unit has, + 1
   uint32_t *words = nullptr, *jall = nullptr;
   double *d_cum = nullptr;
-  int64_t *d_m = nullptr, *d_status = nullptr;
-  uint32_t *d_flags = nullptr;
+  int64_t *d_m = nullptr, *d_status = nullptr;   // per unit: templates kept, draws the decode left
+  uint32_t *d_flags = nullptr;                   // per unit: geometric draws flagged for the host
   BatchPerm bp{nullptr, nullptr};
   // the asynchronous tail (sample_units_async): per unit, its tail's end on stream2; units not yet resolved
   std::vector<hipEvent_t> ev;
   int32_t n_pending = 0;
+  bool two_lanes() const { return n_lanes > 1; }
   ~SampleState() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
 
+// ---- sampling lanes -------------------------------------------------------------------------------------------
+// A lane runs one unit's stages at a time on a stream and scratch of its own (the units' stages are latency-bound, so
+// two units side by side fill the chip better than one after the other).  Lane 0 is the main stream with
+// s[S_TS..S_HEADS]; lane 1 is stream2 with lane2[].
+struct SampleLane {
+  hipStream_t st;
+  DevBuf &ts, &ts_shuf, &te, &keep, &sort_keys, &sort_vals, &heads, &sort_tmp;
+  DevBuf &scan;     // the scans' partials / look-back scratch
+  size_t tot_off;   // the geometric scan's total, in d_small
+};
+
+static SampleLane sample_lane(mh_ctx *ctx, int lane) {
+  if (lane == 0) {
+    DevBuf *s = ctx->s;
+    return SampleLane{ctx->stream, s[mh_ctx::S_TS], s[mh_ctx::S_TS_SHUF], s[mh_ctx::S_TE], s[mh_ctx::S_KEEP],
+                      s[mh_ctx::S_SORT_KEYS], s[mh_ctx::S_SORT_VALS], s[mh_ctx::S_HEADS], ctx->perm_tmp,
+                      ctx->scan_partials, 128};
+  }
+  DevBuf *b = ctx->lane2;
+  return SampleLane{ctx->stream2, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], ctx->scan_partials2, 192};
+}
+
+// The lane's buffers for units of up to nn - 1 draws (sort_tmp is sized by the sort itself)
+static int32_t lane_reserve(mh_ctx *ctx, const SampleLane &L, int64_t nn) {
+  MH_TRY(ensure(ctx, L.ts, 8 * nn));
+  MH_TRY(ensure(ctx, L.ts_shuf, 8 * nn));
+  MH_TRY(ensure(ctx, L.te, 8 * nn));
+  MH_TRY(ensure(ctx, L.keep, nn));
+  MH_TRY(ensure(ctx, L.sort_keys, 4 * (nn + 1)));
+  MH_TRY(ensure(ctx, L.sort_vals, 4 * (nn + 1)));
+  MH_TRY(ensure(ctx, L.heads, 4 * nn));
+  MH_TRY(ensure(ctx, L.scan, std::max<size_t>(16 * scan_partials_count(nn + 1) + 64,
+                                              scan_lb_scratch_bytes<int64_t>(nn + 1))));
+  return MH_OK;
+}
+
+// Lane 1 starts after what the main stream has queued so far / the main stream goes on after what lane 1 has queued.
+static int32_t lanes_fork(mh_ctx *ctx) {
+  HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+  HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+  return MH_OK;
+}
+static int32_t lanes_join(mh_ctx *ctx) {
+  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+  HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+  return MH_OK;
+}
+
+// The permutation's (target, step) sort: n keys (values: their indices) by the bits that hold n, on stream st with
+// `tmp` as the sort's scratch.  The hand-written LSD radix sort of mh_sort.h (9-bit digits with the tile counts folded
+// into the scatter: a 64 M-draw batch's 27-bit keys in 3 passes, 512-thread workgroups that fit beside the FASTQ
+// writers; round 5's A/B against rocprim's onesweep: within noise).
+static int32_t sort_targets(mh_ctx *ctx, hipStream_t st, const uint32_t *keys_in, uint32_t *keys_out,
+                            uint32_t *vals_out, int64_t n, DevBuf &tmp) {
+  unsigned end_bit = 1;
+  while (end_bit < 32 && ((int64_t)1 << end_bit) < n) end_bit++;
+  size_t bytes = 0;
+  HIPCHK(ctx, lsd_sort_pairs_iota(nullptr, bytes, keys_in, keys_out, vals_out, n, end_bit, st));
+  MH_TRY(ensure(ctx, tmp, bytes + 256));
+  HIPCHK(ctx, lsd_sort_pairs_iota(tmp.p, bytes, keys_in, keys_out, vals_out, n, end_bit, st));
+  return MH_OK;
+}
+
+// ---- one unit's stages on a lane ---------------------------------------------------------------------------------
+// Unit u's start positions, the cumulative sum of its geometric draws, into `ts`.  `exact`: materialise the draws
+// (s[S_EXACT_DRAWS], reserved by the caller) and recompute the flagged ones on the host (rare path).
+static int32_t unit_geometric_scan(mh_ctx *ctx, const SampleState &S, const SampleLane &L, int32_t u, bool exact,
+                                   int64_t *ts) {
+  const UnitPlan &q = S.plan[u];
+  hipStream_t st = L.st;
+  StageStreamScope on_lane(ctx, st);
+  const int64_t n = q.n;
+  const double p = S.p;
+  const uint32_t *w_tloc = S.words + q.w_tloc;
+  uint32_t *d_flag = S.d_flags + u;
+  int64_t *flag_idx = (int64_t *)ctx->s[mh_ctx::S_FLAG_IDX].p;
+  int64_t *tot = (int64_t *)((char *)ctx->d_small.p + L.tot_off);
+  const double log_q = std::log(1.0 - p);
+  GeoFlags fl{flag_idx, d_flag, 1024};
+
+  stage_begin(ctx, "sample_geometric_scan");
+  if (!exact) {
+    HIPCHK(ctx, device_scan_sum<int64_t>(st, n, LoadGeo{w_tloc, p, log_q, fl}, StoreTs{ts, q.p_min + 1, q.ni},
+                                         L.scan.p, tot));
+  } else {
+    int64_t *g = (int64_t *)ctx->s[mh_ctx::S_EXACT_DRAWS].p;
+    uint32_t nflag = 0;
+    HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4, st));
+    hipLaunchKernelGGL(k_geo_array, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, n, w_tloc, p, log_q, fl, g);
+    HIPCHK(ctx, hipMemcpyAsync(&nflag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    SYNCCHK(ctx, hipStreamSynchronize(st));
+    auto host_geo = [&](const uint32_t *ww) {   // numpy legacy_random_geometric_inversion on the host libm
+      double U = (((int32_t)(ww[0] >> 5)) * 67108864.0 + ((int32_t)(ww[1] >> 6))) / 9007199254740992.0;
+      return (int64_t)std::ceil(std::log1p(-U) / std::log(1.0 - p));
+    };
+    if (ctx->force_geo && p < 0.333333333333333333333333) {
+      // MH_DEC_FORCE_GEO (tests): every draw of the unit from the host libm, so this path is pinned against the
+      // oracle on whole units, not only on the rare draws the device flags
+      std::vector<uint32_t> hw(2 * (size_t)n);
+      std::vector<int64_t> hg((size_t)n);
+      HIPCHK(ctx, hipMemcpy(hw.data(), w_tloc, 8 * (size_t)n, hipMemcpyDeviceToHost));
+      for (int64_t k = 0; k < n; k++) hg[k] = host_geo(hw.data() + 2 * k);
+      HIPCHK(ctx, hipMemcpy(g, hg.data(), 8 * (size_t)n, hipMemcpyHostToDevice));
+    } else {
+      if (nflag > 1024) return arg_fail(ctx, MH_E_ARG, "too many near-integer geometric quotients");
+      std::vector<int64_t> idx(nflag);
+      if (nflag) HIPCHK(ctx, hipMemcpy(idx.data(), flag_idx, 8 * nflag, hipMemcpyDeviceToHost));
+      for (int64_t k : idx) {
+        uint32_t ww[2];
+        HIPCHK(ctx, hipMemcpy(ww, w_tloc + 2 * k, 8, hipMemcpyDeviceToHost));
+        int64_t gv = host_geo(ww);   // the reference's libm
+        HIPCHK(ctx, hipMemcpy(g + k, &gv, 8, hipMemcpyHostToDevice));
+      }
+    }
+    HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4, st));
+    HIPCHK(ctx, device_scan<int64_t>(st, n, LoadArr{g}, StoreTs{ts, q.p_min + 1, q.ni}, OpSum{}, (int64_t)0,
+                                     (int64_t *)L.scan.p, tot));
+  }
+  stage_end(ctx);
+  return MH_OK;
+}
+
+// Unit u's own permutation of the lane's ts into its ts_shuf: the steps sorted by (target, step) — keys j, values the
+// step index — the heads, the chase.  (Two stage records, as the batch path's sort and chase give.)
+static int32_t unit_permutation(mh_ctx *ctx, const SampleState &S, const SampleLane &L, int32_t u) {
+  const UnitPlan &q = S.plan[u];
+  hipStream_t st = L.st;
+  StageStreamScope on_lane(ctx, st);
+  const int64_t n = q.n;
+  uint32_t *sk = (uint32_t *)L.sort_keys.p, *sv = (uint32_t *)L.sort_vals.p;
+  int32_t *nxt = (int32_t *)L.heads.p;
+  stage_begin(ctx, "sample_permutation");
+  MH_TRY(sort_targets(ctx, st, S.jall + q.j_off, sk, sv, n, L.sort_tmp));
+  HIPCHK(ctx, hipMemsetAsync(nxt, 0xff, 4 * (size_t)n, st));
+  hipLaunchKernelGGL(k_perm_heads, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, n, (const uint32_t *)sk,
+                     (const uint32_t *)sv, nxt);
+  HIPCHK(ctx, hipGetLastError());
+  stage_end(ctx);
+  stage_begin(ctx, "sample_permutation");
+  hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(n, 256, INT32_MAX)), dim3(256), 0, st, (int64_t)0, n,
+                     (const uint32_t *)sk, (const uint32_t *)sv, (const int32_t *)nxt, (const int64_t *)L.ts.p,
+                     (int64_t *)L.ts_shuf.p);
+  HIPCHK(ctx, hipGetLastError());
+  stage_end(ctx);
+  return MH_OK;
+}
+
+// Unit u's template lengths from the start positions `ts`, then keep + compaction into its template set, file order.
+static int32_t unit_tlen_compact(mh_ctx *ctx, const SampleState &S, const SampleLane &L, int32_t u,
+                                 const int64_t *ts) {
+  const UnitPlan &q = S.plan[u];
+  hipStream_t st = L.st;
+  StageStreamScope on_lane(ctx, st);
+  const int64_t n = q.n;
+  int64_t *te = (int64_t *)L.te.p;
+  uint8_t *keep = (uint8_t *)L.keep.p;
+  stage_begin(ctx, "sample_tlen_compact");
+  hipLaunchKernelGGL(k_tlen, dim3(grid_for((n + TLEN_PER - 1) / TLEN_PER, 256, INT32_MAX)), dim3(256), 8 * S.n_tlen,
+                     st, n, S.words + q.w_tlen, (const double *)S.d_cum, S.n_tlen, (int64_t)S.rlen, q.p_max, ts, te,
+                     keep);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, device_scan_sum<int64_t>(st, n, LoadKeep{keep},
+                                       StoreCompact{keep, ts, te, (int64_t *)q.out->pos0.p, (int64_t *)q.out->pos1.p,
+                                                    (int64_t)S.rlen, S.words + q.w_fo, (int8_t *)q.out->fo0.p,
+                                                    q.out->has_n0 ? (int32_t *)q.out->n0.p : nullptr},
+                                       L.scan.p, S.d_m + u));
+  stage_end(ctx);
+  return MH_OK;
+}
+
+// Everything after the word streams for unit u on one lane (the per-unit path, the fix-ups)
+static int32_t unit_whole(mh_ctx *ctx, const SampleState &S, const SampleLane &L, int32_t u, bool exact) {
+  MH_TRY(unit_geometric_scan(ctx, S, L, u, exact, (int64_t *)L.ts.p));
+  const bool permute = S.rng_mode == MH_RNG_MITTY && S.plan[u].n > 1;
+  if (permute) MH_TRY(unit_permutation(ctx, S, L, u));
+  return unit_tlen_compact(ctx, S, L, u, (const int64_t *)(permute ? L.ts_shuf.p : L.ts.p));
+}
+
+// Where the batch path's tails find unit u's start positions: shuffled (one draw has nothing to shuffle)
+static const int64_t *batch_ts(const SampleState &S, int32_t u) {
+  const UnitPlan &q = S.plan[u];
+  return (q.n > 1 ? S.bp.tsh : S.bp.ts) + q.j_off;
+}
+
+// The rare exact fix-up of unit u, on lane 0: its decode ran out of words (status: the single-stream decode), or it
+// has near-integer geometric quotients (flag: the draws recomputed by the host libm).  *m: the templates it keeps.
+static int32_t unit_fixup(mh_ctx *ctx, const SampleState &S, int32_t u, int64_t status, uint32_t flag, int64_t *m) {
+  const UnitPlan &q = S.plan[u];
+  hipStream_t st = ctx->stream;
+  if (S.rng_mode == MH_RNG_MITTY && status != 0) {
+    hipLaunchKernelGGL(k_shuffle_decode, dim3(1), dim3(SD_THREADS), 0, st, q.s_shuf, q.n, S.jall + q.j_off);
+    HIPCHK(ctx, hipGetLastError());
+  }
+  MH_TRY(ensure(ctx, ctx->s[mh_ctx::S_EXACT_DRAWS], 8 * (size_t)S.nn));
+  HIPCHK(ctx, hipMemsetAsync(S.d_flags + u, 0, 4, st));
+  MH_TRY(unit_whole(ctx, S, sample_lane(ctx, 0), u, flag != 0));
+  HIPCHK(ctx, hipMemcpyAsync(m, S.d_m + u, 8, hipMemcpyDeviceToHost, st));
+  SYNCCHK(ctx, hipStreamSynchronize(st));
+  ctx->fixups++;
+  return MH_OK;
+}
+
+// ---- the batch's head, piece by piece -------------------------------------------------------------------------
 // One unit's draws and its four word streams' seeds and offsets in the batch word buffer (readgenerate's
 // illumina.generate_reads: int((p_max - p_min) * p * 1.2) draws; the seeds from the unit's RandomState)
 static void plan_unit_words(UnitPlan &q, int64_t p_min, int64_t p_max, uint64_t seed, double p, int32_t rng_mode,
@@ -1378,7 +1497,6 @@ static void plan_unit_words(UnitPlan &q, int64_t p_min, int64_t p_max, uint64_t 
 
 // The unit's four MT19937 streams as jump-ahead segments into `words`
 static void unit_seg_jobs(uint32_t *words, const UnitPlan &q, std::vector<SegJob> &jobs, int64_t &kmax) {
-  const int64_t SEG_WORDS = seg_words();
   auto add_stream = [&](uint32_t *out, int64_t count, uint32_t seed) {
     for (int64_t k = 0; k * SEG_WORDS < count; k++) {
       int64_t s0 = k * SEG_WORDS;
@@ -1392,29 +1510,20 @@ static void unit_seg_jobs(uint32_t *words, const UnitPlan &q, std::vector<SegJob
   add_stream(words + q.w_shuf, q.n_shuf_words, q.s_shuf);
 }
 
-// First half: plan, word streams, shuffle decode, geometric scans and — batch path — the permutation's sort and
-// heads; the per-unit path runs its units whole here.
-static int32_t sample_head(mh_ctx *ctx, SampleState &S, int32_t n_units, const int32_t *tpl_ids, const int64_t *p_min,
-                           const int64_t *p_max, const uint64_t *seeds, double p, int32_t rlen, const double *cum_tlen,
-                           int32_t n_tlen, int32_t rng_mode, const NodeIdx *nidx) {
-  for (int32_t u = 0; u < n_units; u++)
-    if (seeds[u] > 0xffffffffull)
-      return arg_fail(ctx, MH_E_SEED, "Seed value " + std::to_string(seeds[u]) + " is out of range 0 - 4294967295");
-  if (n_tlen <= 0 || n_tlen > 8192) return arg_fail(ctx, MH_E_ARG, "cum_tlen must have 1..8192 entries");
-  if (rng_mode != MH_RNG_MITTY && rng_mode != MH_RNG_PHILOX) return arg_fail(ctx, MH_E_ARG, "unknown rng_mode");
-  MH_TRY(tpl_resolve_all(ctx));   // the previous batch's asynchronous tail reads the batch buffers this one refills
-  hipStream_t st = ctx->stream;
-
-  // ---- plan ---------------------------------------------------------------------------------------------------
-  std::vector<UnitPlan> plan(n_units);
-  int64_t words_total = 0, j_total = 0, n_max = 1;
-  for (int32_t u = 0; u < n_units; u++) {
-    UnitPlan &q = plan[u];
-    plan_unit_words(q, p_min[u], p_max[u], seeds[u], p, rng_mode, words_total);
+// The plan (S.plan, j_total, nn) and every unit's template set reserved for its draws; *words_total: the batch's words.
+static int32_t plan_units(mh_ctx *ctx, SampleState &S, const int32_t *tpl_ids, const int64_t *p_min,
+                          const int64_t *p_max, const uint64_t *seeds, const NodeIdx *nidx, int64_t *words_total) {
+  S.plan.assign(S.n_units, UnitPlan{});
+  int64_t n_max = 1;
+  *words_total = 0;
+  S.j_total = 0;
+  for (int32_t u = 0; u < S.n_units; u++) {
+    UnitPlan &q = S.plan[u];
+    plan_unit_words(q, p_min[u], p_max[u], seeds[u], S.p, S.rng_mode, *words_total);
     // (< 2^30 draws: the permutation sort's look-back counts are 30-bit; a 2x150 30x unit of 2^30 draws is a
     // 36 Gbp region)
     if (q.n > ((int64_t)1 << 30) - 8) return arg_fail(ctx, MH_E_ARG, "region too large for one work unit");
-    q.j_off = j_total; j_total += q.n + 4;
+    q.j_off = S.j_total; S.j_total += q.n + 4;
     n_max = std::max(n_max, q.n);
     TplSet &ts = ctx->tsets[tpl_ids[u]];
     MH_TRY(wait_unused(ctx, ts.used, ts.used_set));   // a queued FASTQ writer may still read the old templates
@@ -1428,205 +1537,185 @@ static int32_t sample_head(mh_ctx *ctx, SampleState &S, int32_t n_units, const i
     ts.valid = false;
     q.out = &ts;
   }
-  const int64_t nn = n_max + 1;
+  S.nn = n_max + 1;
   ctx->batch_left = 0;
-  for (const UnitPlan &q : plan) ctx->batch_left += q.n;
-  // this batch's word streams generated ahead by the prefetch thread (prefetch_words, same plan): its buffer becomes
-  // the batch's (the previous batch's tails, which read the old one, were resolved above)
-  PrefetchedWords &pw = ctx->pf_words;
-  const bool have_words = rng_mode == MH_RNG_MITTY && pw.valid && pw.p == p && pw.seeds.size() == (size_t)n_units &&
-                          std::equal(pw.seeds.begin(), pw.seeds.end(), seeds) &&
-                          std::equal(pw.p_min.begin(), pw.p_min.end(), p_min) &&
-                          std::equal(pw.p_max.begin(), pw.p_max.end(), p_max) && pw.words_total == words_total;
-  pw.valid = false;
-  if (have_words) std::swap(ctx->s[0], pw.buf);
-  MH_TRY(ensure(ctx, ctx->s[0], 4 * (size_t)words_total + 64));
-  MH_TRY(ensure(ctx, ctx->s[3], 4 * (size_t)j_total + 64));
-  MH_TRY(ensure(ctx, ctx->s[4], 8 * nn));
-  MH_TRY(ensure(ctx, ctx->s[5], 8 * nn));
-  MH_TRY(ensure(ctx, ctx->s[6], 8 * nn));
-  MH_TRY(ensure(ctx, ctx->s[7], nn));
-  MH_TRY(ensure(ctx, ctx->s[8], 4 * (nn + 1)));
-  MH_TRY(ensure(ctx, ctx->s[9], 4 * (nn + 1)));
-  MH_TRY(ensure(ctx, ctx->s[10], 4 * nn));
-  MH_TRY(ensure(ctx, ctx->s[11], 8 * 1024));
-  // sampling lanes for the per-unit stages: two (four let more of the sampling run beside the FASTQ writers, which
-  // then take longer: 3.45 against 2.73 ms per launch), at most one per unit
-  int n_lanes = std::max(1, std::min(2, (int)n_units));
-  const bool two_lanes = n_lanes > 1;
-  // lanes 2 and 3 get their streams on first use only: the box runs with 4 hardware queues per process
-  // (GPU_MAX_HW_QUEUES), and streams beyond that share queues — a sampling lane sharing the writer's queue would
-  // serialize behind it
-  for (int l = 2; l < n_lanes; l++)
-    if (!ctx->xstream[l - 2]) {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->xstream[l - 2], hipStreamNonBlocking, hi));
-      HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_xjoin[l - 2], hipEventDisableTiming));
-    }
-  for (int l = 1; l < n_lanes; l++) {
-    mh::DevBuf *L = l == 1 ? ctx->lane2 : ctx->xlane[l - 2];
-    MH_TRY(ensure(ctx, L[0], 8 * nn));
-    MH_TRY(ensure(ctx, L[1], 8 * nn));
-    MH_TRY(ensure(ctx, L[2], 8 * nn));
-    MH_TRY(ensure(ctx, L[3], nn));
-    MH_TRY(ensure(ctx, L[4], 4 * (nn + 1)));
-    MH_TRY(ensure(ctx, L[5], 4 * (nn + 1)));
-    MH_TRY(ensure(ctx, L[6], 4 * nn));
-    MH_TRY(ensure(ctx, l == 1 ? ctx->scan_partials2 : ctx->xscan[l - 2],
-                  std::max<size_t>(16 * scan_partials_count(nn + 1) + 64, scan_lb_scratch_bytes<int64_t>(nn + 1))));
-  }
-  MH_TRY(ensure(ctx, ctx->s[13], 8 * (size_t)n_tlen + 64));
-  MH_TRY(ensure(ctx, ctx->s[1], 64 * (size_t)n_units + 64));          // per-unit m, flags, decode status
-  MH_TRY(ensure(ctx, ctx->d_small, 8192 + 256));
-  MH_TRY(ensure(ctx, ctx->scan_partials, std::max<size_t>(16 * scan_partials_count(nn + 1) + 64,
-                                                           scan_lb_scratch_bytes<int64_t>(nn + 1))));
-  uint32_t *words = (uint32_t *)ctx->s[0].p, *jall = (uint32_t *)ctx->s[3].p;
-  double *d_cum = (double *)ctx->s[13].p;
-  int64_t *d_m = (int64_t *)ctx->s[1].p;                                // [n_units]
-  int64_t *d_status = d_m + n_units;                                    // [n_units]
-  uint32_t *d_flags = (uint32_t *)(d_status + n_units);                 // [n_units]
-  HIPCHK(ctx, hipMemsetAsync(ctx->s[1].p, 0, 64 * (size_t)n_units + 64, st));
-  HIPCHK(ctx, hipMemcpyAsync(d_cum, cum_tlen, 8 * n_tlen, hipMemcpyHostToDevice, st));
+  for (const UnitPlan &q : S.plan) ctx->batch_left += q.n;
+  return MH_OK;
+}
 
-  stage_begin(ctx, "sample");
-  // ---- word streams ------------------------------------------------------------------------------------------
-  if (rng_mode == MH_RNG_MITTY) {
+// The batch buffers and the lanes reserved for the plan; S's pointers into them; the per-unit results cleared and the
+// template length table uploaded.  *have_words: the word buffer is the one the prefetch thread filled for this plan.
+static int32_t reserve_batch(mh_ctx *ctx, SampleState &S, const int64_t *p_min, const int64_t *p_max,
+                             const uint64_t *seeds, const double *cum_tlen, int64_t words_total, bool *have_words) {
+  hipStream_t st = ctx->stream;
+  const int32_t n_units = S.n_units;
+  // this batch's word streams generated ahead by the prefetch thread (prefetch_words, same plan): its buffer becomes
+  // the batch's (the previous batch's tails, which read the old one, were resolved by sample_head)
+  PrefetchedWords &pw = ctx->pf_words;
+  *have_words = S.rng_mode == MH_RNG_MITTY && pw.valid && pw.p == S.p && pw.seeds.size() == (size_t)n_units &&
+                std::equal(pw.seeds.begin(), pw.seeds.end(), seeds) &&
+                std::equal(pw.p_min.begin(), pw.p_min.end(), p_min) &&
+                std::equal(pw.p_max.begin(), pw.p_max.end(), p_max) && pw.words_total == words_total;
+  pw.valid = false;
+  DevBuf &b_words = ctx->s[mh_ctx::S_WORDS], &b_j = ctx->s[mh_ctx::S_J], &b_cum = ctx->s[mh_ctx::S_CUM_TLEN];
+  DevBuf &b_unit = ctx->s[mh_ctx::S_UNIT];
+  if (*have_words) std::swap(b_words, pw.buf);
+  MH_TRY(ensure(ctx, b_words, 4 * (size_t)words_total + 64));
+  MH_TRY(ensure(ctx, b_j, 4 * (size_t)S.j_total + 64));
+  MH_TRY(ensure(ctx, ctx->s[mh_ctx::S_FLAG_IDX], 8 * 1024));   // GeoFlags' 1024 indices
+  MH_TRY(ensure(ctx, b_cum, 8 * (size_t)S.n_tlen + 64));
+  MH_TRY(ensure(ctx, b_unit, 64 * (size_t)n_units + 64));      // per-unit m, decode status, flags
+  MH_TRY(ensure(ctx, ctx->d_small, 8192 + 256));
+  for (int l = 0; l < S.n_lanes; l++) MH_TRY(lane_reserve(ctx, sample_lane(ctx, l), S.nn));
+  S.words = (uint32_t *)b_words.p;
+  S.jall = (uint32_t *)b_j.p;
+  S.d_cum = (double *)b_cum.p;
+  S.d_m = (int64_t *)b_unit.p;                         // [n_units]
+  S.d_status = S.d_m + n_units;                        // [n_units]
+  S.d_flags = (uint32_t *)(S.d_status + n_units);      // [n_units]
+  HIPCHK(ctx, hipMemsetAsync(b_unit.p, 0, 64 * (size_t)n_units + 64, st));
+  HIPCHK(ctx, hipMemcpyAsync(S.d_cum, cum_tlen, 8 * S.n_tlen, hipMemcpyHostToDevice, st));
+  return MH_OK;
+}
+
+// Every unit's word streams into S.words and — --rng mitty — its shuffle's swap indices decoded into S.jall
+static int32_t word_streams(mh_ctx *ctx, const SampleState &S, bool have_words) {
+  hipStream_t st = ctx->stream;
+  if (S.rng_mode == MH_RNG_MITTY) {
     std::vector<SegJob> jobs;
     std::vector<DecJob> dec;
     int64_t kmax = 0;
-    const int64_t SEG_WORDS = seg_words();
-    for (int32_t u = 0; u < n_units; u++) {
-      UnitPlan &q = plan[u];
+    for (int32_t u = 0; u < S.n_units; u++) {
+      const UnitPlan &q = S.plan[u];
       if (q.n == 0) continue;
-      unit_seg_jobs(words, q, jobs, kmax);
-      dec.push_back(DecJob{words + q.w_shuf, q.n_shuf_words, q.n, jall + q.j_off, d_status + u});
+      unit_seg_jobs(S.words, q, jobs, kmax);
+      dec.push_back(DecJob{S.words + q.w_shuf, q.n_shuf_words, q.n, S.jall + q.j_off, S.d_status + u});
     }
-    if (!jobs.empty()) {
-      MH_TRY(ensure_polys(ctx, st, kmax, SEG_WORDS));
-      MH_TRY(ensure(ctx, ctx->s[2], sizeof(SegJob) * jobs.size() + sizeof(DecJob) * dec.size() + 64));
-      SegJob *d_jobs = (SegJob *)ctx->s[2].p;
-      DecJob *d_dec = (DecJob *)((char *)ctx->s[2].p + ((sizeof(SegJob) * jobs.size() + 15) / 16) * 16);
-      HIPCHK(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(ctx, hipMemcpyAsync(d_dec, dec.data(), sizeof(DecJob) * dec.size(), hipMemcpyHostToDevice, st));
-      if (!have_words) {
-        stage_begin(ctx, "sample_mt_segments");
-        hipLaunchKernelGGL(k_mt_segments, dim3((unsigned)jobs.size()), dim3(256), 0, st, (const SegJob *)d_jobs,
-                           (const uint32_t *)ctx->jump_polys.p);
-        HIPCHK(ctx, hipGetLastError());
-        stage_end(ctx);
-      }
-      stage_begin(ctx, "sample_shuffle_decode");
-      bool done = false;
-      if (!ctx->decode_sequential) MH_TRY(decode_parallel(ctx, dec, d_status, &done));
-      if (!done) {   // no fixed point within the pass budget: the block-sequential decode
-        hipLaunchKernelGGL(k_shuffle_decode2, dim3((unsigned)dec.size()), dim3(DC_THREADS), 0, st,
-                           (const DecJob *)d_dec);
-        HIPCHK(ctx, hipGetLastError());
-      }
+    if (jobs.empty()) return MH_OK;
+    MH_TRY(ensure_polys(ctx, st, kmax, SEG_WORDS));
+    DevBuf &b_jobs = ctx->s[mh_ctx::S_JOBS];   // the segment jobs, then (16-byte aligned) the decode jobs
+    MH_TRY(ensure(ctx, b_jobs, sizeof(SegJob) * jobs.size() + sizeof(DecJob) * dec.size() + 64));
+    SegJob *d_jobs = (SegJob *)b_jobs.p;
+    DecJob *d_dec = (DecJob *)((char *)b_jobs.p + ((sizeof(SegJob) * jobs.size() + 15) / 16) * 16);
+    HIPCHK(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_dec, dec.data(), sizeof(DecJob) * dec.size(), hipMemcpyHostToDevice, st));
+    if (!have_words) {
+      stage_begin(ctx, "sample_mt_segments");
+      hipLaunchKernelGGL(k_mt_segments, dim3((unsigned)jobs.size()), dim3(256), 0, st, (const SegJob *)d_jobs,
+                         (const uint32_t *)ctx->jump_polys.p);
+      HIPCHK(ctx, hipGetLastError());
       stage_end(ctx);
-      // keep the job tables alive until the kernels ran
-      SYNCCHK(ctx, hipStreamSynchronize(st));
     }
+    stage_begin(ctx, "sample_shuffle_decode");
+    bool done = false;
+    if (!ctx->decode_sequential) MH_TRY(decode_parallel(ctx, dec, S.d_status, &done));
+    if (!done) {   // no fixed point within the pass budget: the block-sequential decode
+      hipLaunchKernelGGL(k_shuffle_decode2, dim3((unsigned)dec.size()), dim3(DC_THREADS), 0, st,
+                         (const DecJob *)d_dec);
+      HIPCHK(ctx, hipGetLastError());
+    }
+    stage_end(ctx);
+    // keep the job tables alive until the kernels ran
+    SYNCCHK(ctx, hipStreamSynchronize(st));
   } else {
-    for (int32_t u = 0; u < n_units; u++) {
-      UnitPlan &q = plan[u];
+    for (int32_t u = 0; u < S.n_units; u++) {
+      const UnitPlan &q = S.plan[u];
       if (q.n == 0) continue;
       uint64_t key = ((uint64_t)q.s_tloc << 32) | q.s_tlen;
       hipLaunchKernelGGL(k_philox_words, dim3(grid_for((2 * q.n + 3) / 4, 256, INT32_MAX)), dim3(256), 0, st,
-                         words + q.w_tloc, 2 * q.n, key, 1u);
+                         S.words + q.w_tloc, 2 * q.n, key, 1u);
       hipLaunchKernelGGL(k_philox_words, dim3(grid_for((2 * q.n + 3) / 4, 256, INT32_MAX)), dim3(256), 0, st,
-                         words + q.w_tlen, 2 * q.n, key, 2u);
+                         S.words + q.w_tlen, 2 * q.n, key, 2u);
       hipLaunchKernelGGL(k_philox_words, dim3(grid_for((q.n_fo_words + 3) / 4, 256, INT32_MAX)), dim3(256), 0, st,
-                         words + q.w_fo, q.n_fo_words, key, 3u);
+                         S.words + q.w_fo, q.n_fo_words, key, 3u);
       HIPCHK(ctx, hipGetLastError());
     }
   }
+  return MH_OK;
+}
+
+// The batch-wide permutation's first half, after the lanes' fork: every unit's geometric scan into the batch ts (the
+// lanes, joined here), then on the main stream one sort of every unit's (target, step) and the heads.  The chase is
+// the tails'.
+static int32_t batch_permutation_head(mh_ctx *ctx, SampleState &S) {
+  hipStream_t st = ctx->stream;
+  const int32_t n_units = S.n_units;
+  const int64_t j_total = S.j_total;
+  // pb: ts, shuffled ts, global keys, sorted keys, sorted steps, heads — one entry per j entry of the batch
+  MH_TRY(ensure(ctx, ctx->pb[0], 8 * (size_t)j_total + 64));
+  MH_TRY(ensure(ctx, ctx->pb[1], 8 * (size_t)j_total + 64));
+  for (int b = 2; b < 6; b++) MH_TRY(ensure(ctx, ctx->pb[b], 4 * (size_t)j_total + 64));
+  S.bp = BatchPerm{(int64_t *)ctx->pb[0].p, (int64_t *)ctx->pb[1].p};
+  for (int32_t u = 0, k = 0; u < n_units; u++) {
+    if (S.plan[u].n == 0) continue;
+    MH_TRY(unit_geometric_scan(ctx, S, sample_lane(ctx, k++ % S.n_lanes), u, false, S.bp.ts + S.plan[u].j_off));
+  }
+  if (S.two_lanes()) MH_TRY(lanes_join(ctx));
+  stage_begin(ctx, "sample_permutation");
+  std::vector<int64_t> spans(2 * (size_t)n_units);   // every unit's offset in the batch, then every unit's draws
+  for (int32_t u = 0; u < n_units; u++) {
+    spans[u] = S.plan[u].j_off;
+    spans[n_units + u] = S.plan[u].n;
+  }
+  DevBuf &b_spans = ctx->s[mh_ctx::S_UNIT_SPANS];
+  MH_TRY(ensure(ctx, b_spans, 16 * (size_t)n_units + 64));
+  int64_t *d_uo = (int64_t *)b_spans.p;
+  HIPCHK(ctx, hipMemcpyAsync(d_uo, spans.data(), 8 * n_units, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(d_uo + n_units, spans.data() + n_units, 8 * n_units, hipMemcpyHostToDevice, st));
+  uint32_t *gk = (uint32_t *)ctx->pb[2].p, *sk = (uint32_t *)ctx->pb[3].p, *sv = (uint32_t *)ctx->pb[4].p;
+  int32_t *nxt = (int32_t *)ctx->pb[5].p;
+  hipLaunchKernelGGL(k_perm_keys, dim3(grid_for(j_total, 256, INT32_MAX)), dim3(256), 0, st, j_total,
+                     (const uint32_t *)S.jall, (const int64_t *)d_uo, (const int64_t *)(d_uo + n_units), n_units, gk,
+                     nxt);
+  HIPCHK(ctx, hipGetLastError());
+  MH_TRY(sort_targets(ctx, st, gk, sk, sv, j_total, ctx->pb_tmp));
+  hipLaunchKernelGGL(k_perm_heads, dim3(grid_for(j_total, 256, INT32_MAX)), dim3(256), 0, st, j_total,
+                     (const uint32_t *)sk, (const uint32_t *)sv, nxt);
+  HIPCHK(ctx, hipGetLastError());
+  stage_end(ctx);
+  return MH_OK;
+}
+
+// First half: plan, word streams, shuffle decode, geometric scans and — batch path — the permutation's sort and
+// heads; the per-unit path runs its units whole here.
+static int32_t sample_head(mh_ctx *ctx, SampleState &S, int32_t n_units, const int32_t *tpl_ids, const int64_t *p_min,
+                           const int64_t *p_max, const uint64_t *seeds, double p, int32_t rlen, const double *cum_tlen,
+                           int32_t n_tlen, int32_t rng_mode, const NodeIdx *nidx) {
+  for (int32_t u = 0; u < n_units; u++)
+    if (seeds[u] > 0xffffffffull)
+      return arg_fail(ctx, MH_E_SEED, "Seed value " + std::to_string(seeds[u]) + " is out of range 0 - 4294967295");
+  if (n_tlen <= 0 || n_tlen > 8192) return arg_fail(ctx, MH_E_ARG, "cum_tlen must have 1..8192 entries");
+  if (rng_mode != MH_RNG_MITTY && rng_mode != MH_RNG_PHILOX) return arg_fail(ctx, MH_E_ARG, "unknown rng_mode");
+  MH_TRY(tpl_resolve_all(ctx));   // the previous batch's asynchronous tail reads the batch buffers this one refills
+  S.n_units = n_units;
+  S.rng_mode = rng_mode;
+  S.rlen = rlen;
+  S.n_tlen = n_tlen;
+  S.p = p;
+  // sampling lanes for the per-unit stages: two (four let more of the sampling run beside the FASTQ writers, which
+  // then take longer: 3.45 against 2.73 ms per launch), at most one per unit
+  S.n_lanes = std::max(1, std::min(2, (int)n_units));
+  int64_t words_total = 0;
+  bool have_words = false;
+  MH_TRY(plan_units(ctx, S, tpl_ids, p_min, p_max, seeds, nidx, &words_total));
+  MH_TRY(reserve_batch(ctx, S, p_min, p_max, seeds, cum_tlen, words_total, &have_words));
+
+  stage_begin(ctx, "sample");
+  MH_TRY(word_streams(ctx, S, have_words));
 
   // ---- per-unit parallel stages (stream-ordered, shared scratch) ------------------------------------------------
   // units alternate between the two lanes; the second lane forks after the word streams and joins before readback.
   // (They overlap the FASTQ writers queued earlier: the radix sorts and look-back scans run several times slower beside
   // a bandwidth-bound writer than alone, but waiting for the writers to drain left the writer stream idle instead —
   // the same step time, round 2.)
-  if (two_lanes) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    for (int l = 2; l < n_lanes; l++) HIPCHK(ctx, hipStreamWaitEvent(ctx->xstream[l - 2], ctx->ev_fork, 0));
-  }
+  if (S.two_lanes()) MH_TRY(lanes_fork(ctx));
   // the batch-wide permutation (one sort per unit when the batch's draws exceed 2^30)
-  const bool batch = rng_mode == MH_RNG_MITTY && j_total < ((int64_t)1 << 30) && n_units <= PK_UNITS;
-  if (batch) {
-    MH_TRY(ensure(ctx, ctx->pb[0], 8 * (size_t)j_total + 64));
-    MH_TRY(ensure(ctx, ctx->pb[1], 8 * (size_t)j_total + 64));
-    for (int b = 2; b < 6; b++) MH_TRY(ensure(ctx, ctx->pb[b], 4 * (size_t)j_total + 64));
-    BatchPerm bp{(int64_t *)ctx->pb[0].p, (int64_t *)ctx->pb[1].p};
-    // 1. every unit's geometric cumsum into the batch ts (lanes)
-    for (int32_t u = 0, k = 0; u < n_units; u++) {
-      if (plan[u].n == 0) continue;
-      MH_TRY(finish_unit(ctx, plan[u], words, jall + plan[u].j_off, p, rlen, d_cum, n_tlen, rng_mode, false, d_m + u,
-                         d_flags + u, k++ % n_lanes, 1, &bp));
-    }
-    if (two_lanes) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-      HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-      for (int l = 2; l < n_lanes; l++) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev_xjoin[l - 2], ctx->xstream[l - 2]));
-        HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_xjoin[l - 2], 0));
-      }
-    }
-    // 2. one sort of every unit's (target, step), heads, chase (main stream)
-    stage_begin(ctx, "sample_permutation");
-    std::vector<int64_t> uo(n_units), un(n_units);
-    for (int32_t u = 0; u < n_units; u++) {
-      uo[u] = plan[u].j_off;
-      un[u] = plan[u].n;
-    }
-    int64_t *d_uo = (int64_t *)ctx->s[12].p;
-    MH_TRY(ensure(ctx, ctx->s[12], 16 * (size_t)n_units + 64));
-    d_uo = (int64_t *)ctx->s[12].p;
-    HIPCHK(ctx, hipMemcpyAsync(d_uo, uo.data(), 8 * n_units, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_uo + n_units, un.data(), 8 * n_units, hipMemcpyHostToDevice, st));
-    uint32_t *gk = (uint32_t *)ctx->pb[2].p, *sk = (uint32_t *)ctx->pb[3].p, *sv = (uint32_t *)ctx->pb[4].p;
-    int32_t *nxt = (int32_t *)ctx->pb[5].p;
-    hipLaunchKernelGGL(k_perm_keys, dim3(grid_for(j_total, 256, INT32_MAX)), dim3(256), 0, st, j_total,
-                       (const uint32_t *)jall, (const int64_t *)d_uo, (const int64_t *)(d_uo + n_units), n_units, gk,
-                       nxt);
-    HIPCHK(ctx, hipGetLastError());
-    unsigned end_bit = 1;
-    while (end_bit < 32 && ((int64_t)1 << end_bit) < j_total) end_bit++;
-    size_t tmp = 0;
-    HIPCHK(ctx, perm_sort(nullptr, tmp, gk, sk, sv, (size_t)j_total, end_bit, st));
-    MH_TRY(ensure(ctx, ctx->pb_tmp, tmp + 256));
-    HIPCHK(ctx, perm_sort(ctx->pb_tmp.p, tmp, gk, sk, sv, (size_t)j_total, end_bit, st));
-    hipLaunchKernelGGL(k_perm_heads, dim3(grid_for(j_total, 256, INT32_MAX)), dim3(256), 0, st, j_total,
-                       (const uint32_t *)sk, (const uint32_t *)sv, nxt);
-    HIPCHK(ctx, hipGetLastError());
-    stage_end(ctx);
-    S.bp = bp;
-  } else {
-    for (int32_t u = 0, k = 0; u < n_units; u++) {
-      if (plan[u].n == 0) continue;
-      MH_TRY(finish_unit(ctx, plan[u], words, jall + plan[u].j_off, p, rlen, d_cum, n_tlen, rng_mode, false, d_m + u,
-                         d_flags + u, k++ % n_lanes));
-    }
+  S.batch = rng_mode == MH_RNG_MITTY && S.j_total < ((int64_t)1 << 30) && n_units <= PK_UNITS;
+  if (S.batch) return batch_permutation_head(ctx, S);
+  for (int32_t u = 0, k = 0; u < n_units; u++) {
+    if (S.plan[u].n == 0) continue;
+    MH_TRY(unit_whole(ctx, S, sample_lane(ctx, k++ % S.n_lanes), u, false));
   }
-  S.plan = std::move(plan);
-  S.n_units = n_units;
-  S.rng_mode = rng_mode;
-  S.rlen = rlen;
-  S.n_tlen = n_tlen;
-  S.n_lanes = n_lanes;
-  S.two_lanes = two_lanes;
-  S.batch = batch;
-  S.p = p;
-  S.j_total = j_total;
-  S.nn = nn;
-  S.words = words;
-  S.jall = jall;
-  S.d_cum = d_cum;
-  S.d_m = d_m;
-  S.d_status = d_status;
-  S.d_flags = d_flags;
   return MH_OK;
 }
 
@@ -1634,87 +1723,55 @@ static int32_t sample_head(mh_ctx *ctx, SampleState &S, int32_t n_units, const i
 // the counts read back, the rare exact fix-ups, the template sets marked valid.
 static int32_t sample_tail(mh_ctx *ctx, SampleState &S, int64_t *out_n) {
   hipStream_t st = ctx->stream;
-  std::vector<UnitPlan> &plan = S.plan;
-  const int32_t n_units = S.n_units, rng_mode = S.rng_mode, rlen = S.rlen, n_tlen = S.n_tlen, n_lanes = S.n_lanes;
-  const bool two_lanes = S.two_lanes;
-  const double p = S.p;
-  const int64_t j_total = S.j_total, nn = S.nn;
-  uint32_t *words = S.words, *jall = S.jall;
-  double *d_cum = S.d_cum;
-  int64_t *d_m = S.d_m, *d_status = S.d_status;
-  uint32_t *d_flags = S.d_flags;
+  const int32_t n_units = S.n_units;
   if (S.batch) {
-    const BatchPerm &bp = S.bp;
     const uint32_t *sk = (const uint32_t *)ctx->pb[3].p, *sv = (const uint32_t *)ctx->pb[4].p;
     const int32_t *nxt = (const int32_t *)ctx->pb[5].p;
     stage_begin(ctx, "sample_permutation");
-    hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(j_total, 256, INT32_MAX)), dim3(256), 0, st, (int64_t)0, j_total,
-                       sk, sv, nxt, (const int64_t *)bp.ts, bp.tsh);
+    hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(S.j_total, 256, INT32_MAX)), dim3(256), 0, st, (int64_t)0,
+                       S.j_total, sk, sv, nxt, (const int64_t *)S.bp.ts, S.bp.tsh);
     HIPCHK(ctx, hipGetLastError());
     stage_end(ctx);
-    // 3. every unit's template lengths, compaction and file order (lanes)
-    if (two_lanes) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-      for (int l = 2; l < n_lanes; l++) HIPCHK(ctx, hipStreamWaitEvent(ctx->xstream[l - 2], ctx->ev_fork, 0));
-    }
+    // every unit's template lengths, compaction and file order (lanes)
+    if (S.two_lanes()) MH_TRY(lanes_fork(ctx));
     for (int32_t u = 0, k = 0; u < n_units; u++) {
-      if (plan[u].n == 0) continue;
-      MH_TRY(finish_unit(ctx, plan[u], words, jall + plan[u].j_off, p, rlen, d_cum, n_tlen, rng_mode, false, d_m + u,
-                         d_flags + u, k++ % n_lanes, 2, &bp));
+      if (S.plan[u].n == 0) continue;
+      MH_TRY(unit_tlen_compact(ctx, S, sample_lane(ctx, k++ % S.n_lanes), u, batch_ts(S, u)));
     }
   }
-  if (two_lanes) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-    for (int l = 2; l < n_lanes; l++) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_xjoin[l - 2], ctx->xstream[l - 2]));
-      HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_xjoin[l - 2], 0));
-    }
-  }
+  if (S.two_lanes()) MH_TRY(lanes_join(ctx));
   std::vector<int64_t> hm(n_units), hstat(n_units);
   std::vector<uint32_t> hflag(n_units);
-  // d_m, d_status, d_flags are consecutive in s[1] (20 bytes per unit): one readback into pinned memory
+  // d_m, d_status, d_flags are consecutive in s[S_UNIT] (20 bytes per unit): one readback into pinned memory
   int64_t *hs = pinned_small(ctx);
   const size_t rb_bytes = 20 * (size_t)n_units;
   if (hs && rb_bytes <= 3072) {
-    HIPCHK(ctx, hipMemcpyAsync(hs + 64, d_m, rb_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hs + 64, S.d_m, rb_bytes, hipMemcpyDeviceToHost, st));
     SYNCCHK(ctx, hipStreamSynchronize(st));
     std::memcpy(hm.data(), hs + 64, 8 * n_units);
     std::memcpy(hstat.data(), hs + 64 + n_units, 8 * n_units);
     std::memcpy(hflag.data(), hs + 64 + 2 * n_units, 4 * n_units);
   } else {
-    HIPCHK(ctx, hipMemcpyAsync(hm.data(), d_m, 8 * n_units, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(hstat.data(), d_status, 8 * n_units, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(hflag.data(), d_flags, 4 * n_units, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hm.data(), S.d_m, 8 * n_units, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hstat.data(), S.d_status, 8 * n_units, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hflag.data(), S.d_flags, 4 * n_units, hipMemcpyDeviceToHost, st));
     SYNCCHK(ctx, hipStreamSynchronize(st));
   }
 
   // ---- rare exact fix-ups: decode out of words (sequential stream), near-integer geometric quotients ------------
   for (int32_t u = 0; u < n_units; u++) {
-    UnitPlan &q = plan[u];
-    if (q.n == 0) continue;
+    if (S.plan[u].n == 0) continue;
     // MH_DEC_FORCE_FIXUP / _GEO (tests): take the fallback for every unit
     if (ctx->force_fixup) hstat[u] = 1;
     if (ctx->force_geo) hflag[u] = 1;
     if (hstat[u] == 0 && hflag[u] == 0) continue;
-    if (rng_mode == MH_RNG_MITTY && hstat[u] != 0) {
-      hipLaunchKernelGGL(k_shuffle_decode, dim3(1), dim3(SD_THREADS), 0, st, q.s_shuf, q.n, jall + q.j_off);
-      HIPCHK(ctx, hipGetLastError());
-    }
-    MH_TRY(ensure(ctx, ctx->s[12], 8 * (size_t)nn));
-    HIPCHK(ctx, hipMemsetAsync(d_flags + u, 0, 4, st));
-    MH_TRY(finish_unit(ctx, q, words, jall + q.j_off, p, rlen, d_cum, n_tlen, rng_mode, hflag[u] != 0, d_m + u,
-                       d_flags + u));
-    HIPCHK(ctx, hipMemcpyAsync(&hm[u], d_m + u, 8, hipMemcpyDeviceToHost, st));
-    SYNCCHK(ctx, hipStreamSynchronize(st));
-    ctx->fixups++;
+    MH_TRY(unit_fixup(ctx, S, u, hstat[u], hflag[u], &hm[u]));
   }
   stage_end(ctx);
   for (int32_t u = 0; u < n_units; u++) {
-    TplSet &ts = *plan[u].out;
-    ts.n = plan[u].n == 0 ? 0 : hm[u];
-    ts.rlen = rlen;
+    TplSet &ts = *S.plan[u].out;
+    ts.n = S.plan[u].n == 0 ? 0 : hm[u];
+    ts.rlen = S.rlen;
     ts.valid = true;
     if (out_n) out_n[u] = ts.n;
   }
@@ -1737,17 +1794,14 @@ __global__ void k_unit_result(const int64_t *m, const int64_t *status, const uin
 // stay pending (TplSet.pend) until tpl_resolve.
 static int32_t sample_tail_async(mh_ctx *ctx, const std::shared_ptr<SampleState> &Sp) {
   SampleState &S = *Sp;
-  std::vector<UnitPlan> &plan = S.plan;
-  const int32_t n_units = S.n_units;
-  hipStream_t st = ctx->stream, l1 = ctx->stream2;
-  const BatchPerm &bp = S.bp;
+  const SampleLane L1 = sample_lane(ctx, 1);
+  hipStream_t l1 = L1.st;
   const uint32_t *sk = (const uint32_t *)ctx->pb[3].p, *sv = (const uint32_t *)ctx->pb[4].p;
   const int32_t *nxt = (const int32_t *)ctx->pb[5].p;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
-  HIPCHK(ctx, hipStreamWaitEvent(l1, ctx->ev_fork, 0));
-  S.ev.assign(n_units, nullptr);
-  for (int32_t u = 0; u < n_units; u++) {
-    UnitPlan &q = plan[u];
+  MH_TRY(lanes_fork(ctx));
+  S.ev.assign(S.n_units, nullptr);
+  for (int32_t u = 0; u < S.n_units; u++) {
+    const UnitPlan &q = S.plan[u];
     TplSet &ts = *q.out;
     if (q.n == 0) {
       ts.n = 0;
@@ -1756,16 +1810,16 @@ static int32_t sample_tail_async(mh_ctx *ctx, const std::shared_ptr<SampleState>
       continue;
     }
     // (the whole batch's chase on the main stream before the fork instead: the same step time, round 4's A/B)
-    ctx->stage_stream = l1;
-    stage_begin(ctx, "sample_permutation");
-    const int64_t k0 = q.j_off, k1 = q.j_off + q.n + 4;
-    hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(k1 - k0, 256, INT32_MAX)), dim3(256), 0, l1, k0, k1, sk, sv, nxt,
-                       (const int64_t *)bp.ts, bp.tsh);
-    stage_end(ctx);
-    ctx->stage_stream = nullptr;
+    {
+      StageStreamScope on_lane(ctx, l1);
+      stage_begin(ctx, "sample_permutation");
+      const int64_t k0 = q.j_off, k1 = q.j_off + q.n + 4;
+      hipLaunchKernelGGL(k_perm_chase, dim3(grid_for(k1 - k0, 256, INT32_MAX)), dim3(256), 0, l1, k0, k1, sk, sv, nxt,
+                         (const int64_t *)S.bp.ts, S.bp.tsh);
+      stage_end(ctx);
+    }
     HIPCHK(ctx, hipGetLastError());
-    MH_TRY(finish_unit(ctx, q, S.words, S.jall + q.j_off, S.p, S.rlen, S.d_cum, S.n_tlen, S.rng_mode, false,
-                       S.d_m + u, S.d_flags + u, 1, 2, &bp));
+    MH_TRY(unit_tlen_compact(ctx, S, L1, u, batch_ts(S, u)));
     hipLaunchKernelGGL(k_unit_result, dim3(1), dim3(64), 0, l1, (const int64_t *)(S.d_m + u),
                        (const int64_t *)(S.d_status + u), (const uint32_t *)(S.d_flags + u), ctx->d_units + 4 * u);
     HIPCHK(ctx, hipGetLastError());
@@ -1787,27 +1841,13 @@ int32_t tpl_resolve(mh_ctx *ctx, TplSet &ts) {
   if (!Sp || u >= Sp->n_units || Sp->plan[u].out != &ts)
     return arg_fail(ctx, MH_E_STATE, "template set of a lost sampling batch");
   SampleState &S = *Sp;
-  UnitPlan &q = S.plan[u];
-  hipStream_t st = ctx->stream;
   SYNCCHK(ctx, hipEventSynchronize(S.ev[u]));
   const volatile int64_t *r = ctx->h_units + 4 * u;
   int64_t m = r[0];
   const int64_t status = ctx->force_fixup ? 1 : r[1];                // MH_DEC_FORCE_FIXUP (tests)
   const uint32_t flag = ctx->force_geo ? 1u : (uint32_t)r[2];         // MH_DEC_FORCE_GEO (tests)
-  HIPCHK(ctx, hipStreamWaitEvent(st, S.ev[u], 0));   // (the main stream's work on this set comes after its tail)
-  if (status != 0 || flag != 0) {   // rare exact fix-up, as in sample_tail
-    if (S.rng_mode == MH_RNG_MITTY && status != 0) {
-      hipLaunchKernelGGL(k_shuffle_decode, dim3(1), dim3(SD_THREADS), 0, st, q.s_shuf, q.n, S.jall + q.j_off);
-      HIPCHK(ctx, hipGetLastError());
-    }
-    MH_TRY(ensure(ctx, ctx->s[12], 8 * (size_t)S.nn));
-    HIPCHK(ctx, hipMemsetAsync(S.d_flags + u, 0, 4, st));
-    MH_TRY(finish_unit(ctx, q, S.words, S.jall + q.j_off, S.p, S.rlen, S.d_cum, S.n_tlen, S.rng_mode, flag != 0,
-                       S.d_m + u, S.d_flags + u));
-    HIPCHK(ctx, hipMemcpyAsync(&m, S.d_m + u, 8, hipMemcpyDeviceToHost, st));
-    SYNCCHK(ctx, hipStreamSynchronize(st));
-    ctx->fixups++;
-  }
+  HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, S.ev[u], 0));   // (the main stream's work on this set comes after its tail)
+  if (status != 0 || flag != 0) MH_TRY(unit_fixup(ctx, S, u, status, flag, &m));
   ts.n = m;
   ts.rlen = S.rlen;
   ts.valid = true;
@@ -1839,7 +1879,7 @@ int32_t prefetch_words(mh_ctx *ctx, hipStream_t st, int32_t n_units, const int64
   for (const UnitPlan &q : plan)
     if (q.n > 0) unit_seg_jobs((uint32_t *)pw.buf.p, q, jobs, kmax);
   // the jump polynomials are the main thread's (ensure_polys): without them resident the batch is not prefetched
-  if (jobs.empty() || ctx->jump_k < kmax + 1 || ctx->jump_seg != seg_words()) return MH_OK;
+  if (jobs.empty() || ctx->jump_k < kmax + 1 || ctx->jump_seg != SEG_WORDS) return MH_OK;
   MH_TRY(ensure(ctx, pw.jobs, sizeof(SegJob) * jobs.size() + 64));
   HIPCHK(ctx, hipMemcpyAsync(pw.jobs.p, jobs.data(), sizeof(SegJob) * jobs.size(), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_mt_segments, dim3((unsigned)jobs.size()), dim3(256), 0, st, (const SegJob *)pw.jobs.p,
@@ -1871,7 +1911,7 @@ int32_t sample_units_async(mh_ctx *ctx, int32_t n_units, const int32_t *tpl_ids,
   auto S = std::make_shared<SampleState>();
   MH_TRY(sample_head(ctx, *S, n_units, tpl_ids, p_min, p_max, seeds, p, rlen, cum_tlen, n_tlen, rng_mode, nidx));
   // the per-unit path (Philox, oversized batches) and a one-unit batch (no second lane) end as sample_units does
-  if (!S->batch || !S->two_lanes) return sample_tail(ctx, *S, nullptr);
+  if (!S->batch || !S->two_lanes()) return sample_tail(ctx, *S, nullptr);
   return sample_tail_async(ctx, S);
 }
 

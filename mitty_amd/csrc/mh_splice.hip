@@ -542,8 +542,8 @@ int32_t splice_build(mh_ctx *ctx, Hap &h, const Contig &c, int64_t rs, const Var
   const bool l1 = lane != 0;
   hipStream_t st = lane == 2 ? ctx->pstream : l1 ? ctx->stream2 : ctx->stream;
   DevBuf *sl = lane == 2 ? ctx->sl3 : ctx->sl2;
-  DevBuf &b_anchor = l1 ? sl[0] : ctx->s[6], &b_acc = l1 ? sl[1] : ctx->s[7];
-  DevBuf &b_refb = l1 ? sl[2] : ctx->s[8], &b_nsrc = l1 ? sl[3] : ctx->s[9];
+  DevBuf &b_anchor = l1 ? sl[0] : ctx->s[mh_ctx::S_SPL_ANCHOR], &b_acc = l1 ? sl[1] : ctx->s[mh_ctx::S_SPL_ACC];
+  DevBuf &b_refb = l1 ? sl[2] : ctx->s[mh_ctx::S_SPL_REFB], &b_nsrc = l1 ? sl[3] : ctx->s[mh_ctx::S_SPL_NSRC];
   DevBuf &b_small = l1 ? sl[4] : ctx->d_small, &b_part = l1 ? sl[5] : ctx->scan_partials;
   DevBuf &b_nrun = l1 ? sl[6] : ctx->nrun_tmp, &b_perm = l1 ? sl[7] : ctx->perm_tmp;
   auto stage_begin = [&](mh_ctx *cx, const char *name) {
@@ -565,7 +565,7 @@ int32_t splice_build(mh_ctx *ctx, Hap &h, const Contig &c, int64_t rs, const Var
   const int64_t *d_aoff = (const int64_t *)v.aoff.p, *d_alen = (const int64_t *)v.alen.p;
   const uint8_t *d_op = (const uint8_t *)v.op.p, *d_pool = (const uint8_t *)v.pool.p;
 
-  // --- scratch: anchor(6) accepted(7) ref_before(8) node src(9) small(d_small) -----------------------------
+  // --- scratch: anchor, accepted, ref_before, node src (first lane: s[S_SPL_*]), small (d_small) ------------
   MH_TRY(ensure(ctx, b_anchor, nv));
   MH_TRY(ensure(ctx, b_acc, nv));
   MH_TRY(ensure(ctx, b_refb, 8 * nv));

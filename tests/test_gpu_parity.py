@@ -69,8 +69,8 @@ DEC_MODES = {'sequential': 1, 'force_fixup': 2, 'force_geo': 4, 'all': 7}
 def test_templates_forced_fallbacks_vs_oracle(native, mode):
   """The exact fallbacks that keep the templates bit-exact when the fast path cannot, each forced through the C ABI
   (mh_set_decode_mode) on a 12 Mbp unit (illumina.py:66-76): the block-sequential decode (k_shuffle_decode2), the
-  single-stream decode + per-unit permutation fix-up (k_shuffle_decode, finish_unit), and every geometric draw
-  recomputed by the host libm (finish_unit's exact path).  Array-equal to the oracle; the fix-up modes must have run."""
+  single-stream decode + per-unit permutation fix-up (k_shuffle_decode, unit_fixup), and every geometric draw
+  recomputed by the host libm (unit_geometric_scan's exact path).  Array-equal to the oracle; the fix-up modes must have run."""
   from mitty_amd.simulation import illumina
   from oracle import oracle as O
   mdl = G.model('hiseq-X-v2.5-Garvan')
@@ -759,6 +759,88 @@ def test_async_tail_equals_sync_templates(native):
         assert len(g[0]) == ns[k % 5]
         for a, b in zip(g, w):
           assert np.array_equal(a, b), (rep, k)
+  finally:
+    eng.close()
+
+
+def test_per_unit_path_two_lanes_vs_oracle(native):
+  """More than PK_UNITS = 512 units in one --rng mitty batch: no batch-wide permutation, every unit's own geometric
+  scan, sort, heads, chase and compaction, alternating between the two sampling lanes (illumina.py:66-76).  513 units
+  over three small haplotypes — zero draws, a handful of templates, around a thousand — in an irregular order, so
+  both lanes see all three kinds and zero-draw units fall between non-empty ones.  Every unit array-equal to the
+  oracle; mh_sample_units_async (which ends such a batch as mh_sample_units does) gives the same arrays."""
+  from mitty_amd import _native, synth
+  from mitty_amd.engine import Engine
+  from oracle import oracle as O
+  mdl = G.model('hiseq-X-v2.5-Garvan')
+  p, _ = _native.read_model_params(150, 30.0)
+  lens = [30, 400, 40_000]
+  seqs = [synth.contig(L, 81 + i, n_gaps=False) for i, L in enumerate(lens)]
+  n_units = 513
+  which = np.random.RandomState(83).randint(0, 3, size=n_units)
+  seeds = [9000 + 3 * k for k in range(n_units)]
+  eng = Engine(0)
+  try:
+    haps = []
+    for ri, s in enumerate(seqs):
+      eng.load_region(ri, (str(ri + 1), 0, len(s)), s)
+      haps.append(eng.haplotype(ri, 0, synth.copies_soa(synth.variants(s, 91 + ri))[0]))
+    want = [O.generate_templates(p, 150, mdl['cum_tlen'], haps[h][2], haps[h][3], sd) for h, sd in zip(which, seeds)]
+    counts = np.array([len(w[0]) for w in want])
+    draws = np.array([int((haps[h][3] - haps[h][2]) * p * 1.2) for h in which])
+    assert counts.min() == 0 and (draws == 0).any() and counts.max() > 500
+    assert ((counts > 0) & (counts < 20)).any()
+    # the lanes take the units with draws in turn: every kind with draws on both of them, and at both index parities
+    lane = np.cumsum(draws > 0) - 1
+    for h in (1, 2):
+      assert {int(lane[k]) % 2 for k in range(n_units) if which[k] == h and counts[k] > 0} == {0, 1}
+    assert all((counts[par::2] > 0).any() for par in (0, 1))
+    inner = np.nonzero(draws == 0)[0]
+    assert any(0 < k < n_units - 1 and draws[k - 1] > 0 and draws[k + 1] > 0 for k in inner)
+    slots = [haps[h][0] for h in which]
+    ns = eng.ctx.sample_units(list(range(n_units)), slots, seeds, p, 150, mdl['cum_tlen'])
+    assert np.array_equal(ns, counts)
+    eng.ctx.sample_units_async(list(range(1000, 1000 + n_units)), slots, seeds, p, 150, mdl['cum_tlen'])
+    for base in (0, 1000):
+      for k, w in enumerate(want):
+        got = eng.ctx.templates_export(base + k)
+        for a, b in zip(got, w):
+          assert np.array_equal(a, b), (base, k, int(which[k]))
+  finally:
+    eng.close()
+
+
+def test_sampling_stage_accounting(native):
+  """The stages a three-unit --rng mitty batch opens (enable_timing), by name and count, words generated in the call:
+  one batch stage, one word-stream and one decode stage, a geometric scan and a template-length compaction per unit;
+  the permutation is the batch's sort and heads plus one chase for mh_sample_units, plus one chase per unit for
+  mh_sample_units_async's tails."""
+  from collections import Counter
+  from mitty_amd import _native, synth
+  from mitty_amd.engine import Engine
+  mdl = G.model('hiseq-X-v2.5-Garvan')
+  p, _ = _native.read_model_params(150, 30.0)
+  L = 1_000_000
+  seq = synth.contig(L, 85)
+  eng = Engine(0)
+  try:
+    eng.load_region(0, ('4', 0, L), seq)
+    slot = eng.haplotype(0, 0, synth.copies_soa(synth.variants(seq, 86))[0])[0]
+    seeds = [5100, 5101, 5102]
+
+    def sample_stages():
+      return Counter(nm for nm, _ in eng.ctx.stage_times() if nm.startswith('sample'))
+
+    eng.ctx.enable_timing(True)
+    ns = eng.ctx.sample_units([0, 1, 2], [slot] * 3, seeds, p, 150, mdl['cum_tlen'])
+    assert min(ns) > 1000 and eng.ctx.fixup_count() == 0
+    want = {'sample': 1, 'sample_mt_segments': 1, 'sample_shuffle_decode': 1, 'sample_geometric_scan': 3,
+            'sample_permutation': 2, 'sample_tlen_compact': 3}
+    assert sample_stages() == want
+    eng.ctx.sample_units_async([10, 11, 12], [slot] * 3, seeds, p, 150, mdl['cum_tlen'])
+    assert [eng.ctx.template_count(10 + i) for i in range(3)] == list(ns)
+    assert eng.ctx.fixup_count() == 0
+    assert sample_stages() == dict(want, sample_permutation=4)
   finally:
     eng.close()
 
