@@ -24,6 +24,7 @@
  *   mh_read_model_params  illumina.read_model_params                     mitty/simulation/illumina.py:12-40
  *   mh_bamfile_next       pysam.AlignmentFile.fetch                      mitty/benchmarking/mq.py:61-62
  *   mh_score_add_records  mq / derr process_bam_part                     mitty/benchmarking/mq.py:50-68, derr.py:53-76
+ *   mh_filter_add_records filter-bam (a stub in the reference)           mitty/cli.py:207-221
  *   mh_model_add_records  bam2illumina.process_bam_section               mitty/empirical/bam2illumina.py:17-59, 84-105
  *   mh_cov_add_records    gc.gc_and_coverage_for_region's pileup         mitty/empirical/gc.py:37-38, 43-59
  *   mh_cov_gc             gc.gc_and_coverage_for_region's seq.count      mitty/empirical/gc.py:32-36
@@ -54,7 +55,8 @@ enum {
   MH_E_COMPLEX_VARIANT = -5,  /* a variant that is not SNP/INS/DEL (vcfio.py:124 ValueError) */
   MH_E_SEED = -6,             /* seed outside 0..2^32-1 (illumina.py:53-54 ValueError) */
   MH_E_STATE = -7,            /* call out of order (e.g. emit before sampling) */
-  MH_E_NO_DEVICE = -8         /* no HIP device */
+  MH_E_NO_DEVICE = -8,        /* no HIP device */
+  MH_E_IO = -9                /* an output file could not be created, written or closed (OSError in the facade) */
 };
 
 enum { MH_RNG_MITTY = 0, MH_RNG_PHILOX = 1 };
@@ -445,6 +447,39 @@ int32_t mh_score_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, cons
 int32_t mh_score_add_store(mh_ctx *ctx);
 int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64_t *counts);
 int32_t mh_score_reset(mh_ctx *ctx);
+
+/* ---- filter-bam: a BAM's records kept by alignment error (the reference's stub, cli.py:207-221: after aligning simulated
+ * reads, keep or discard records by how wrong their alignment is).  The score of a record is the scoring section's
+ * (one device function serves both), the verdict, in this order:
+ *   1. tid < 0, or a qname that does not start with the sample prefix: kept iff keep_unscored; the qname is not parsed
+ *   2. otherwise the record is scored; an unparseable qname, a read2 record on a one-group qname and a tid past the
+ *      names fail the session as they fail the scorers (MAPQ >= 100 does not: there is no matrix row to overflow)
+ *   3. kept iff d_lo <= |d_err| <= d_hi and mq_lo <= MAPQ <= mq_hi  (|d_err| = max_d: another chromosome, or max_d or
+ *      further away)
+ * The kept records, in input order and byte for byte, become a BAM at out_path: the header (magic, l_text, text, n_ref,
+ * the references as given) deflated on the host at level 6 in its own block(s), then the records in blocks of 0xff00
+ * bytes deflated on the device, then the EOF marker.  The blocks are cut at multiples of 0xff00 of the kept stream,
+ * so the file's bytes do not depend on how the records were split over the add calls.
+ *   mh_filter_begin        a new session and its file: references (names NUL-separated, lengths[n_refs]), header text,
+ *                          scoring mode and sample prefix as mh_score_begin, the ranges.  0 <= d_lo <= d_hi <= max_d <=
+ *                          2^20 and 0 <= mq_lo <= mq_hi <= 255, else MH_E_ARG before the file is created; a file that
+ *                          cannot be created is MH_E_IO.  A session still open is aborted first
+ *   mh_filter_add_records  as mh_score_add_records; the chunk is marked, compacted and deflated on the device, and its
+ *                          blocks are written to the file during the next call (or by finish), beside the device work
+ *                          of that call.  Once a record fails, nothing of its chunk or of a later one is written
+ *   mh_filter_finish       waits, writes the last block and the EOF marker, closes; counts[8] = records seen, kept,
+ *                          dropped by |d_err|, dropped by MAPQ (|d_err| in range), unscored for tid < 0, unscored by
+ *                          the sample filter, record bytes seen, record bytes kept.  A failed record is MH_E_ARG with
+ *                          "filtering: record N: <what>" and a failed write MH_E_IO naming the path; either way the
+ *                          file is removed (when it is a regular file), the session is over and the context usable
+ *   mh_filter_abort        the session dropped: its file closed and removed */
+int32_t mh_filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64_t *lengths, const char *header_text,
+                        int64_t header_len, const char *out_path, int32_t max_d, int32_t strict,
+                        const char *sample_prefix, int32_t d_lo, int32_t d_hi, int32_t mq_lo, int32_t mq_hi,
+                        int32_t keep_unscored);
+int32_t mh_filter_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t mh_filter_finish(mh_ctx *ctx, int64_t *counts);
+int32_t mh_filter_abort(mh_ctx *ctx);
 
 /* ---- read model from a BAM: bam2illumina (process_bam_section, mitty/empirical/bam2illumina.py:17-59, summed over
  * the header's first 24 @SQ by process_bam_parallel, :84-105; cli.py:54-68).  One pass over BAM records on the device:

@@ -13,6 +13,7 @@ LIB_PATH = (os.environ.get('MH_LIB') or   # MH_LIB: another build of the library
 
 MH_OK, MH_E_ARG, MH_E_HIP, MH_E_OOM, MH_E_CAPACITY, MH_E_COMPLEX_VARIANT, MH_E_SEED, MH_E_STATE, MH_E_NO_DEVICE = \
   0, -1, -2, -3, -4, -5, -6, -7, -8
+MH_E_IO = -9
 MH_RNG_MITTY, MH_RNG_PHILOX = 0, 1
 
 # Every exported symbol of include/mitty_hip.h (tests check the library exports all of them).
@@ -30,6 +31,7 @@ EXPORTS = ['mh_version', 'mh_device_count', 'mh_create', 'mh_destroy', 'mh_last_
            'mh_vcf_open', 'mh_vcf_error', 'mh_vcf_close', 'mh_vcf_region', 'mh_vcf_copy', 'mh_vcf_filter',
            'mh_bamfile_open', 'mh_bamfile_open_gpu', 'mh_bgzf_inflate_gpu', 'mh_bamfile_error', 'mh_bamfile_header', 'mh_bamfile_next', 'mh_bamfile_close',
            'mh_score_begin', 'mh_score_add_records', 'mh_score_add_store', 'mh_score_result', 'mh_score_reset',
+           'mh_filter_begin', 'mh_filter_add_records', 'mh_filter_finish', 'mh_filter_abort',
            'mh_model_begin', 'mh_model_add_records', 'mh_model_add_store', 'mh_model_result', 'mh_model_reset',
            'mh_cov_begin', 'mh_cov_add_records', 'mh_cov_add_store', 'mh_cov_gc', 'mh_cov_result', 'mh_cov_reset',
            'mh_bq_begin', 'mh_bq_add_records', 'mh_bq_add_store', 'mh_bq_result', 'mh_bq_reset',
@@ -168,6 +170,11 @@ def lib():
   _sig(L, 'mh_score_add_store', [c_vp])
   _sig(L, 'mh_score_result', [c_vp, c_vp, c_vp, c_vp])
   _sig(L, 'mh_score_reset', [c_vp])
+  _sig(L, 'mh_filter_begin', [c_vp, c_i32, ctypes.c_char_p, c_vp, ctypes.c_char_p, c_i64, ctypes.c_char_p, c_i32, c_i32,
+                              ctypes.c_char_p, c_i32, c_i32, c_i32, c_i32, c_i32])
+  _sig(L, 'mh_filter_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
+  _sig(L, 'mh_filter_finish', [c_vp, c_vp])
+  _sig(L, 'mh_filter_abort', [c_vp])
   _sig(L, 'mh_model_begin', [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32])
   _sig(L, 'mh_model_add_records', [c_vp, c_vp, c_i64, c_vp, c_i64])
   _sig(L, 'mh_model_add_store', [c_vp])
@@ -515,6 +522,8 @@ def _raise(rc, msg):
     raise MemoryError(msg)
   if rc == MH_E_NO_DEVICE:
     raise NativeUnavailable('no HIP device visible: ' + msg)
+  if rc == MH_E_IO:
+    raise OSError(msg)
   raise NativeError('libmitty_hip error {}: {}'.format(rc, msg))
 
 
@@ -1058,6 +1067,44 @@ class Context:
 
   def score_reset(self):
     self._chk(self._L.mh_score_reset(self._h))
+
+  # ---- filter-bam ----
+  FILTER_COUNTS = ('seen', 'kept', 'dropped_score', 'dropped_mapq', 'skipped_unplaced', 'skipped_sample', 'bytes_in',
+                   'bytes_kept')
+
+  def filter_begin(self, names, lengths, header_text, out_path, max_d=200, strict=False, sample_prefix=None, d_lo=1,
+                   d_hi=None, mq_lo=0, mq_hi=255, keep_unscored=False):
+    """A new filter session writing the kept records to out_path (mh_filter_begin).  names, lengths: the input BAM's
+    references (names a list or the NUL-separated blob); header_text: the output's header text; d_hi None: max_d."""
+    blob = names if isinstance(names, bytes) else b''.join(n.encode() + b'\0' for n in names)
+    n = blob.count(b'\0')
+    ln = np.ascontiguousarray(lengths if n else [0], dtype=np.int64)
+    if n != len(lengths):
+      raise ValueError('filter_begin: {} reference names, {} lengths'.format(n, len(lengths)))
+    h = header_text.encode() if isinstance(header_text, str) else bytes(header_text)
+    self._chk(self._L.mh_filter_begin(self._h, n, blob if n else None, _ptr(ln), h, len(h), os.fsencode(out_path),
+                                      int(max_d), 1 if strict else 0,
+                                      sample_prefix.encode() if sample_prefix else None, int(d_lo),
+                                      int(max_d if d_hi is None else d_hi), int(mq_lo), int(mq_hi),
+                                      1 if keep_unscored else 0))
+
+  def filter_add_raw(self, recs_addr, nbytes, roff_addr, n):
+    """Queue n records at host addresses (BamFile.next_raw's chunk); a failing record is reported by filter_finish."""
+    self._add_raw(self._L.mh_filter_add_records, recs_addr, nbytes, roff_addr, n)
+
+  def filter_add_records(self, recs, roff):
+    """Queue the records recs[roff[i]:roff[i + 1]] (bytes; int64 offsets)."""
+    self._add_records(self._L.mh_filter_add_records, recs, roff)
+
+  def filter_finish(self):
+    """The last block and the EOF marker written, the file closed; the counts dict (FILTER_COUNTS)."""
+    cnt = np.zeros(8, np.int64)
+    self._chk(self._L.mh_filter_finish(self._h, _ptr(cnt)))
+    return dict(zip(self.FILTER_COUNTS, (int(x) for x in cnt)))
+
+  def filter_abort(self):
+    """The session dropped and its file removed."""
+    self._chk(self._L.mh_filter_abort(self._h))
 
   # ---- read model from a BAM (bam2illumina) ----
   def model_begin(self, n_refs, every=1, min_mq=0, max_bq=94, max_bp=300, max_tlen=1000):

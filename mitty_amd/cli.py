@@ -3,14 +3,15 @@
 Implemented: generate-reads (GPU), corrupt-reads (GPU), god-aligner (GPU), mq-plot and derr-plot (GPU scoring, host
 BAM reader; additive --device), bam2illumina (GPU histograms, host BAM reader; additive --device), gc-cov and bq (GPU
 depth track, block sums and histograms, host BAM reader; additive --device), all five with the additive --gpu-inflate
-(the reader's BGZF blocks inflated on the --device GPU instead of on the host threads), filter-variants
-(host C++), qname, list-read-models.  Additive options on generate-reads: --device,
+(the reader's BGZF blocks inflated on the --device GPU instead of on the host threads), filter-bam (GPU: the
+records scored as mq-plot scores them, the kept ones compacted and deflated on the device; a stub in the reference, its
+options are this build's), filter-variants (host C++), qname, list-read-models.  Additive options on generate-reads: --device,
 --rng {mitty,philox}, --corrupt-seed (fused Philox corruption), --gc-bias CURVE / --gc-seed (the sampled templates
 thinned on the GPU by the GC content of the haplotype bytes they span; CURVE from the new gc-bias-model command, which
 fits it to a gc-cov result: the reference has neither); on corrupt-reads: --device, --rng {mitty,philox}.  Multi-GPU: launch generate-reads under
 `python -m torch.distributed.run --nproc-per-node N -m mitty_amd.cli generate-reads ...` (one process per GPU,
 RCCL); the output files are identical to the one-GPU run.  Out of scope for this build (not on the
-generate-reads path): filter-bam (a stub in the reference), describe-read-model (plotting only).
+generate-reads path): describe-read-model (plotting only).
 """
 import logging
 import os
@@ -276,6 +277,40 @@ def derr_plot(bam, csv, plot, max_v, max_d, strict_scoring, sample_name, threads
   derr_mat = derr.process_bam(bam, max_v, max_d, strict_scoring, sample_name, threads, csv, device=device,
                               gpu_inflate=gpu_inflate)
   derr.plot_derr(derr_mat, plot)
+
+
+@cli.command('filter-bam', short_help='Keep the records of a BAM by alignment error')
+@click.argument('bamin', type=click.Path(exists=True))
+@click.argument('bamout', type=click.Path())
+@click.option('--max-d', type=int, default=200, help='Range of d_err to consider')
+@click.option('--strict-scoring', is_flag=True, help="Don't consider breakpoints when scoring alignment")
+@click.option('--sample-name', help='Score reads from only this sample (the others are unscored)')
+@click.option('--min-derr', type=int, default=1, help='Keep records with |d_err| of at least this')
+@click.option('--max-derr', type=int, default=None,
+              help='Keep records with |d_err| of at most this (default: --max-d).  |d_err| == max_d means another '
+                   'chromosome, or max_d or further away')
+@click.option('--min-mq', type=int, default=0, help='Keep records with MAPQ of at least this')
+@click.option('--max-mq', type=int, default=255, help='Keep records with MAPQ of at most this')
+@click.option('--unscored', type=click.Choice(['drop', 'keep']), default='drop',
+              help='Records that are not scored: unplaced, or not of --sample-name')
+@click.option('--threads', default=2)
+@click.option('--device', default=0, help='HIP device ordinal')
+@click.option('--gpu-inflate', is_flag=True, help="Inflate the BAM's BGZF blocks on the GPU")
+def filter_bam(bamin, bamout, max_d, strict_scoring, sample_name, min_derr, max_derr, min_mq, max_mq, unscored, threads,
+               device, gpu_inflate):
+  """Given a BAM of aligned simulated reads, write the records whose alignment error |d_err| and MAPQ lie in the given
+  ranges to BAMOUT, in input order (the reference has a stub, cli.py:207-221).  With the defaults these are the
+  misaligned reads: exactly the records mq-plot counts outside its d_err = 0 column.  |d_err| == max_d means another
+  chromosome, or max_d or further away."""
+  from mitty_amd.benchmarking import filter_bam as fb
+  try:   # (a bad range fails here, before any file or device is touched)
+    fb.check_ranges(max_d, min_derr, max_derr, min_mq, max_mq)
+  except ValueError as e:
+    raise click.BadParameter(str(e))
+  counts = fb.filter_bam(bamin, bamout, max_d=max_d, strict=strict_scoring, sample_name=sample_name, min_derr=min_derr,
+                         max_derr=max_derr, min_mq=min_mq, max_mq=max_mq, unscored=unscored, processes=threads,
+                         device=device, gpu_inflate=gpu_inflate)
+  logging.info('filter-bam: {}'.format(counts))
 
 
 def main():

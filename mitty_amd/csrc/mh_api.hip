@@ -545,6 +545,7 @@ int32_t mh_destroy(mh_ctx *ctx) {
   model_release(ctx->model);
   model_release(ctx->bq);
   cov_release(ctx->cov);
+  filter_release(ctx->filter);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -1856,6 +1857,32 @@ int32_t mh_score_result(mh_ctx *ctx, uint64_t *mq_mat, uint64_t *derr_mat, int64
 int32_t mh_score_reset(mh_ctx *ctx) {
   CTX_GUARD(ctx);
   return score_reset(ctx);
+}
+
+// ---- filter-bam (mh_filter.hip) -----------------------------------------------------------------------------------
+int32_t mh_filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64_t *lengths, const char *header_text,
+                        int64_t header_len, const char *out_path, int32_t max_d, int32_t strict,
+                        const char *sample_prefix, int32_t d_lo, int32_t d_hi, int32_t mq_lo, int32_t mq_hi,
+                        int32_t keep_unscored) {
+  CTX_GUARD(ctx);
+  return filter_begin(ctx, n_refs, names, lengths, header_text, header_len, out_path, max_d, strict, sample_prefix, d_lo,
+                      d_hi, mq_lo, mq_hi, keep_unscored);
+}
+
+int32_t mh_filter_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
+  CTX_GUARD(ctx);
+  MH_TRY(recs_args(ctx, recs, len, roff, n));
+  return filter_add_records(ctx, recs, len, roff, n);
+}
+
+int32_t mh_filter_finish(mh_ctx *ctx, int64_t *counts) {
+  CTX_GUARD(ctx);
+  return filter_finish(ctx, counts);
+}
+
+int32_t mh_filter_abort(mh_ctx *ctx) {
+  CTX_GUARD(ctx);
+  return filter_abort(ctx);
 }
 
 // ---- read model from a BAM: bam2illumina (mh_model.hip) ---------------------------------------------------------

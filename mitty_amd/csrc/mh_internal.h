@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -225,7 +226,7 @@ struct BamStore {
 
 namespace mh {
 
-extern const RecTexts SCORE_TEXTS, MODEL_TEXTS, BQ_TEXTS, COV_TEXTS;   // each beside its session's kernels
+extern const RecTexts SCORE_TEXTS, MODEL_TEXTS, BQ_TEXTS, COV_TEXTS, FILTER_TEXTS;   // each beside its session's kernels
 
 // Alignment scorer (mh_score.hip): both matrices and the counts of one scoring session, resident until read back.
 struct ScoreState {
@@ -268,6 +269,34 @@ struct CovState {
   DevBuf partials;             // the scan's
   DevBuf tab;                  // i64: ln[N_REF] | cbase[N_REF + 1] | bbase[N_REF + 1] for the kernels
   bool scanned = false;        // depth and the covered counts hold the track as it is now
+};
+
+// filter-bam (mh_filter.hip): the session's rule and counts, the kept byte stream on its way into BGZF blocks, and the
+// output file.
+struct FilterState {
+  RecSession ses{FILTER_TEXTS};
+  int32_t max_d = 0, strict = 0, n_refs = 0, plen = 0;
+  int32_t d_lo = 0, d_hi = 0, mq_lo = 0, mq_hi = 0, keep_unscored = 0;
+  DevBuf acc, delta;           // u64[8]: seen, kept, dropped by score / by MAPQ, skipped unplaced / sample, bytes in / kept
+  DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
+  DevBuf ksz;                  // u32 per record of the chunk: its kept bytes (0: dropped)
+  DevBuf klist;                // i64: destination offsets of the kept records (+ the total), then their source offsets
+  DevBuf scan, tot;            // the scan's look-back scratch; its totals (kept bytes, kept records)
+  DevBuf out[2];               // [carry | the chunk's kept bytes]: the chunk being gathered / the next one's carry
+  DevBuf z;                    // the chunk's BGZF blocks
+  int cur = 0;                 // out[cur] holds the carry
+  int64_t carry = 0;           // kept bytes not yet in a block (< 0xff00)
+  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked: a chunk's blocks on their way to the file
+  size_t pin_cap[2] = {0, 0};
+  int64_t pin_len[2] = {0, 0};
+  hipEvent_t ev[2] = {nullptr, nullptr};  // after the copy into pin[k]
+  bool pin_set[2] = {false, false};       // pin[k] holds bytes not yet written
+  int pin_cur = 0;             // the buffer the next chunk's blocks go to
+  int64_t *h_rb = nullptr;     // page-locked: the chunk's totals and the error word
+  FILE *fp = nullptr;
+  std::string path;
+  bool failed = false;         // a record failed: nothing more is written
+  bool io_failed = false;      // a write failed
 };
 
 struct StageTime {
@@ -464,6 +493,8 @@ struct mh_ctx {
   // then, so a steady run allocates and frees nothing per unit
   mh::DevBuf gc_buf;
   mh::DevBuf gc_out[4];
+  // filter-bam session (the newest member stays last: no older field moves)
+  mh::FilterState filter;
 };
 
 namespace mh {
@@ -652,6 +683,15 @@ int32_t cov_result(mh_ctx *ctx, int32_t ref_index, uint32_t *n_n, uint32_t *n_gc
                    int64_t *min_pos, int64_t *max_end, int64_t n_blocks, int64_t *counts);
 int32_t cov_reset(mh_ctx *ctx);
 void cov_release(CovState &S);
+// records kept by alignment error, written as a BAM (mh_filter.hip)
+int32_t filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64_t *lengths, const char *header_text,
+                     int64_t header_len, const char *out_path, int32_t max_d, int32_t strict,
+                     const char *sample_prefix, int32_t d_lo, int32_t d_hi, int32_t mq_lo, int32_t mq_hi,
+                     int32_t keep_unscored);
+int32_t filter_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n);
+int32_t filter_finish(mh_ctx *ctx, int64_t *counts);
+int32_t filter_abort(mh_ctx *ctx);
+void filter_release(FilterState &F);
 int32_t corrupt_fastq(mh_ctx *ctx, const uint8_t *d0, int64_t len0, const uint8_t *d1, int64_t len1, int64_t t_base,
                       int64_t *used0, int64_t *used1, int64_t *templates);
 

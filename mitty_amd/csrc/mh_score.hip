@@ -16,76 +16,37 @@
 //
 // Every read of a record stays inside [roff[i], roff[i + 1]): lengths taken from the record are clamped to it.  A
 // record whose name does not parse (or any other failure) sets the error word with its index and adds nothing.
+//
+// The staging of the heads and the per-record rule (parse_qname, d_err) are mh_scorerec.h's, shared with filter-bam
+// (mh_filter.hip): k_score owns the matrices, the counters and what MAPQ >= 100 means to them.
 #include <algorithm>
 #include <cstring>
 
 #include "mh_internal.h"
+#include "mh_scorerec.h"
 
 namespace mh {
 
 const RecTexts SCORE_TEXTS = {
     "scoring", "call mh_score_begin first",
     "the record store has spilled to the host (mh_bam_set_capacity): score its BAM file",
-    {"", "record shorter than its fixed fields", "tid outside the header's references",
-     "qname does not parse (readgenerate.parse_qname)", "read2 record whose qname has one read group",
-     "MAPQ of 100 or more (mq_mat has 100 rows)"}};
+    {SCORE_KIND_TEXT[0], SCORE_KIND_TEXT[1], SCORE_KIND_TEXT[2], SCORE_KIND_TEXT[3], SCORE_KIND_TEXT[4],
+     SCORE_KIND_TEXT[5]}};
 
 namespace {
 
-constexpr int SC_ROW = 192;       // LDS bytes per record head (4 + 32 fixed bytes, then the name; up to 15 bytes of lead)
 constexpr int SC_NV_LDS = 1026;   // d_err_mat rows with an LDS counter for their d_err = 0 column (max_v_len <= 512)
-constexpr int SC_FIELDS = 13;     // rid, chrom, cpy + 2 x (strand, pos, rlen, cigar, v_list)
-
-enum { SE_STRUCT = 1, SE_TID = 2, SE_PARSE = 3, SE_MATE = 4, SE_MAPQ = 5 };
 
 struct ScoreArgs {
   const uint8_t *recs;
   const int64_t *roff;
   int64_t n, avail;            // records; bytes readable at recs
-  const char *names;           // header names, concatenated
-  const int32_t *name_off;     // [n_refs + 1]
-  int32_t n_refs;
-  const uint8_t *prefix;
-  int32_t plen;
-  int32_t max_d, max_v, strict;
+  ScoreRule rule;              // header names, sample prefix, max_d, strict
+  int32_t max_d, max_v;
   unsigned long long *mq, *dv, *cnt;   // the chunk's sums
   unsigned long long *err;
   int64_t base_rec;
 };
-
-// int() of q[a, b): optional sign, then digits only; values saturate at 2^40.  False when it is not such a number.
-__device__ __forceinline__ bool sc_int(const uint8_t *q, int a, int b, int64_t &v) {
-  if (a >= b) return false;
-  bool neg = false;
-  if (q[a] == '-' || q[a] == '+') { neg = q[a] == '-'; a++; }
-  if (a >= b) return false;
-  int64_t x = 0;
-  for (; a < b; a++) {
-    const uint32_t d = (uint32_t)q[a] - '0';
-    if (d > 9) return false;
-    x = x * 10 + d;
-    if (x > ((int64_t)1 << 40)) x = (int64_t)1 << 40;
-  }
-  v = neg ? -x : x;
-  return true;
-}
-
-// [int(v) for v in v_list.split(',') if v is not '']: false when an item is not a number; *items = the list's length
-__device__ __forceinline__ bool sc_vlist_ok(const uint8_t *q, int a, int b, int *items) {
-  int n = 0, st = a;
-  for (int i = a; i <= b; i++) {
-    if (i == b || q[i] == ',') {
-      if (i > st) {
-        int64_t v;
-        if (!sc_int(q, st, i, v)) return false;
-        n++;
-      }
-      st = i + 1;
-    }
-  }
-  *items = n;
-  return true;
-}
 
 // One add per distinct cell among the wave's lanes (cell < 0: none).  The d_err = 0 column goes to the workgroup's LDS
 // counters (row < lds_rows), everything else to the chunk's matrix in memory.  Called by every lane of the wave.
@@ -110,21 +71,7 @@ __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
   const int64_t tiles = (a.n + 255) / 256;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();   // the counters are zero / the previous tile's rows are no longer read
-    // ---- stage the wave's 64 record heads: one 16-byte load per lane per record, all in flight together
-    const int64_t tw = tile * 256 + 64 * wave;
-    {
-      const int64_t tl = tw + lane;
-      const int64_t s0 = tl < a.n ? a.roff[tl] : 0, e0 = tl < a.n ? a.roff[tl + 1] : 0;
-#pragma unroll 8
-      for (int j = 0; j < 64; j++) {
-        const int64_t s = __shfl(s0, j, 64), e = __shfl(e0, j, 64);
-        const int64_t c0 = s & ~(int64_t)15;
-        int64_t nch = (e - c0 + 15) >> 4;
-        if (nch > SC_ROW / 16) nch = SC_ROW / 16;
-        if (tw + j < a.n && e > s && s >= 0 && c0 + 16 * nch <= a.avail && lane < nch)
-          *(uint4 *)(rows + (64 * wave + j) * SC_ROW + 16 * lane) = *(const uint4 *)(a.recs + c0 + 16 * lane);
-      }
-    }
+    sc_stage_heads(rows, a.recs, a.roff, a.n, a.avail, tile, wave, lane);
     __syncthreads();
     // ---- the thread's record
     const int64_t t = tile * 256 + threadIdx.x;
@@ -139,119 +86,23 @@ __global__ void __launch_bounds__(256) k_score(ScoreArgs a) {
       if (size < 36 || s < 0 || e > a.avail) {
         kind = SE_STRUCT;
       } else {
-        const int64_t c0 = s & ~(int64_t)15;
-        int64_t nch = (e - c0 + 15) >> 4;
-        if (nch > SC_ROW / 16) nch = SC_ROW / 16;
-        const bool row_ok = c0 + 16 * nch <= a.avail;
-        const int64_t rb = 16 * nch - (s - c0);   // the record's bytes in its row
-        const uint8_t *lp = a.recs + s;
-        if (row_ok && rb >= 36) {
-          const uint8_t *rp = rows + threadIdx.x * SC_ROW + (s - c0);
-          if (36 + (int64_t)rp[12] <= rb) lp = rp;   // a name longer than its row is read from memory
-        }
-        const int32_t tid = (int32_t)le32(lp + 4), pos = (int32_t)le32(lp + 8);
-        const int32_t mapq = lp[13], flag = (int32_t)le16(lp + 18);
-        int nmax = lp[12];
-        if (nmax > size - 36) nmax = (int)(size - 36);
-        q = lp + 36;
-        int nlen = 0;
-        while (nlen < nmax && q[nlen] != 0) nlen++;
-        bool pass = true;
-        if (tid < 0) {
-          skip_tid = 1;   // fetch(reference=SN) per @SQ never yields these
-          pass = false;
-        } else if (tid >= a.n_refs) {
-          kind = SE_TID;
-          pass = false;
-        } else if (a.plen > 0) {   // qname.startswith(sample_name)
-          bool eq = nlen >= a.plen;
-          for (int k = 0; eq && k < a.plen; k++) eq = q[k] == a.prefix[k];
-          if (!eq) { skip_smp = 1; pass = false; }
-        }
-        if (pass) {
-          // qname.split('|'): rid, chrom, cpy, then (strand, pos, rlen, cigar, v_list) per read
-          int fs[SC_FIELDS], fe[SC_FIELDS];
-          int nf = 0, st = 0;
-          for (int i = 0; i <= nlen; i++) {
-            if (i == nlen || q[i] == '|') {
-              if (nf < SC_FIELDS) { fs[nf] = st; fe[nf] = i; }
-              nf++;
-              st = i + 1;
-            }
-          }
-          const int ng = nf >= 3 ? (nf - 3) / 5 : 0;   // zip(d[3::5], ..., d[7::5]): whole groups only
-          const int want = (flag & 0x80) ? 1 : 0;
-          int64_t iv;
-          if (nf < 3) kind = SE_PARSE;
-          if (!kind) {   // sample, _ = rid.split(':', 1); int(cpy)
-            bool colon = false;
-            for (int k = fs[0]; k < fe[0]; k++) colon |= q[k] == ':';
-            if (!colon || !sc_int(q, fs[2], fe[2], iv)) kind = SE_PARSE;
-          }
-          int items[2] = {0, 0};
-          for (int g = 0; !kind && g < ng && g < 2; g++) {
-            const int f = 3 + 5 * g;
-            if (!sc_int(q, fs[f], fe[f], iv) || !sc_int(q, fs[f + 1], fe[f + 1], iv) ||
-                !sc_int(q, fs[f + 2], fe[f + 2], iv) || fe[f + 3] <= fs[f + 3] ||
-                !sc_vlist_ok(q, fs[f + 4], fe[f + 4], &items[g]))
-              kind = SE_PARSE;
-          }
-          if (!kind && want >= ng) kind = (want == 1 && ng >= 1) ? SE_MATE : SE_PARSE;
-          if (!kind) {
-            const int f = 3 + 5 * want;
-            int64_t rpos = 0;
-            (void)sc_int(q, fs[f + 1], fe[f + 1], rpos);
-            int cs = fs[f + 3], ce = fe[f + 3];
-            if (q[cs] == '>') {   // '>p:nI' -> 'nI' (parse_qname: split(':')[-1])
-              int k = ce;
-              while (k > cs && q[k - 1] != ':') k--;
-              cs = k;
-            }
-            // reference_name == ri.chrom, as strings
-            const int32_t no = a.name_off[tid], nl = a.name_off[tid + 1] - no;
-            bool same = nl == fe[1] - fs[1];
-            for (int k = 0; same && k < nl; k++) same = a.names[no + k] == (char)q[fs[1] + k];
-            const int64_t p1 = (int64_t)pos + 1, md = a.max_d;
-            int64_t D = md;
-            if (!a.strict && ce <= cs) {
-              kind = SE_PARSE;   // ri.cigar[0] of an empty cigar raises
-            } else if (a.strict || q[cs] == '>') {
-              if (same) D = p1 - rpos > md ? md : (p1 - rpos < -md ? -md : p1 - rpos);
-            } else if (same) {
-              // cigar_parser.findall: (\d+)(\D); '=', 'M', 'X' are breakpoints, 'D' only advances
-              int64_t cp = rpos, cnt = 0;
-              bool have = false;
-              for (int k = cs; k < ce; k++) {
-                const uint32_t d = (uint32_t)q[k] - '0';
-                if (d <= 9) {
-                  cnt = cnt * 10 + d;
-                  if (cnt > ((int64_t)1 << 40)) cnt = (int64_t)1 << 40;
-                  have = true;
-                  continue;
-                }
-                if (have) {
-                  const uint8_t op = q[k];
-                  if (op == '=' || op == 'M' || op == 'X') {
-                    const int64_t df = p1 - cp;
-                    if ((df < 0 ? -df : df) < (D < 0 ? -D : D)) D = df;
-                    cp += cnt;
-                  } else if (op == 'D') {
-                    cp += cnt;
-                  }
-                }
-                cnt = 0;
-                have = false;
-              }
-            }
-            if (!kind && mapq >= 100) kind = SE_MAPQ;   // mq_mat[r.mapq, ...] raises IndexError
-            if (!kind) {
-              col = (int32_t)(D + md);
-              mq_cell = mapq * ncol + col;
-              vs = fs[f + 4];
-              ve = fe[f + 4];
-              v_items = items[want];
-              scored = 1;
-            }
+        const uint8_t *lp = sc_head(rows, a.recs, s, e, a.avail);
+        const ScoreRec r = score_record(lp, size, (int32_t)le16(lp + 18), (int32_t)le32(lp + 4),
+                                        (int32_t)le32(lp + 8), a.rule);
+        q = r.q;
+        kind = r.kind;
+        skip_tid = r.skip_tid;
+        skip_smp = r.skip_smp;
+        if (r.scored) {
+          if (r.mapq >= 100) {
+            kind = SE_MAPQ;   // mq_mat[r.mapq, ...] raises IndexError
+          } else {
+            col = r.d_err + a.max_d;
+            mq_cell = r.mapq * ncol + col;
+            vs = r.vs;
+            ve = r.ve;
+            v_items = r.v_items;
+            scored = 1;
           }
         }
       }
@@ -304,9 +155,11 @@ int32_t score_launch(mh_ctx *ctx, const RecChunk &c) {
   HIPCHK(ctx, hipMemsetAsync(S.delta.p, 0, sizeof(uint64_t) * S.n_all, st));
   unsigned long long *d = (unsigned long long *)S.delta.p;
   const DevBuf &names = c.store ? c.store->names : S.names, &name_off = c.store ? c.store->name_off : S.name_off;
-  ScoreArgs a{c.recs, c.roff, c.n, c.avail, (const char *)names.p, (const int32_t *)name_off.p,
-              c.store ? (int32_t)c.store->ref_names.size() : S.n_refs, (const uint8_t *)S.prefix.p, S.plen, S.max_d,
-              S.max_v, S.strict, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.ses.err.p, c.base_rec};
+  ScoreArgs a{c.recs, c.roff, c.n, c.avail,
+              ScoreRule{(const char *)names.p, (const int32_t *)name_off.p,
+                        c.store ? (int32_t)c.store->ref_names.size() : S.n_refs, (const uint8_t *)S.prefix.p, S.plen,
+                        S.max_d, S.strict},
+              S.max_d, S.max_v, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.ses.err.p, c.base_rec};
   // a workgroup's LDS counters are 32-bit: at most 4096 tiles (2^20 records, < 2^8 list items each) per workgroup
   const int64_t tiles = (c.n + 255) / 256;
   const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
