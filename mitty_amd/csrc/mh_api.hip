@@ -529,8 +529,7 @@ int32_t mh_destroy(mh_ctx *ctx) {
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
   if (ctx->h_small3) (void)hipHostFree(ctx->h_small3);
   if (ctx->h_units) (void)hipHostFree(ctx->h_units);
-  for (uint8_t *p : ctx->h_bam_pin)
-    if (p) (void)hipHostFree(p);
+  ctx->bam_sink.release();
   for (auto &e : ctx->eset) {
     release(e.recs); release(e.off); release(e.tsum); release(e.tpre); release(e.stat); release(e.crrec);
     (void)hipEventDestroy(e.done);
@@ -1977,292 +1976,12 @@ int32_t mh_cov_reset(mh_ctx *ctx) {
 }  // extern "C"
 
 // copies that mh_output_bgzf_pair left in flight out of gz_out's halves: done before anything else rewrites gz_out
-static int32_t gz_drain(mh_ctx *ctx) {
+int32_t mh::gz_drain(mh_ctx *ctx) {
   for (int h = 0; h < 2; h++)
     if (ctx->gz_pending[h]) {
       SYNCCHK(ctx, hipEventSynchronize(ctx->ev_gz[h]));
       ctx->gz_pending[h] = false;
     }
-  return MH_OK;
-}
-
-// Window of a spilled store's deflate: a quarter of the store's capacity (two staging windows in HBM and two ring
-// slots of compressed output, each about a window: together about the capacity), whole BGZF blocks, at most 8192
-// blocks (535 MB)
-static int64_t spill_window(const BamStore &B) {
-  const int64_t cap_blocks = B.cap > 0 ? B.cap / 4 / BGZF_BLOCK : 8192;
-  return std::max<int64_t>(1, std::min<int64_t>(8192, cap_blocks)) * BGZF_BLOCK;
-}
-
-// A spilled store's sorted record stream deflated on the device window by window: the host assembles window i + 1
-// (bam_assemble, a thread of its own) while window i goes H2D and through bgzf_device into ring slot i & 1 of
-// ctx->gz_out (ring bytes per slot; pieces are reported at their ring offsets, the block offsets in `boff` are the
-// stream's).  Before window i overwrites its slot, slot_free(i) returns once the compressed pieces of window i - 2 have
-// left the device.  Windows are whole numbers of BGZF blocks, so the blocks — and the file — are the ones one deflate
-// of the whole stream makes.  The stream deflated is the sorted stream from byte `skip`, then `tail` (a range's part
-// of a file, mh_bam_write_part).
-static int32_t bam_deflate_spilled(mh_ctx *ctx, int64_t ring, int64_t skip, const uint8_t *tail, int64_t tail_len,
-                                   int64_t *nz, std::vector<int64_t> *boff,
-                                   const std::function<void(int64_t, int64_t)> &on_piece,
-                                   const std::function<int32_t(int64_t)> &slot_free) {
-  BamStore &B = ctx->bam;
-  MH_TRY(bam_spill(ctx));   // (the records still in HBM: every record is then on the host)
-  MH_TRY(bam_sort(ctx));    // (a no-op unless the spill undid a direct write's order)
-  BamHostOrder o;
-  MH_TRY(bam_host_order(ctx, o));
-  const int64_t W = spill_window(B);
-  const int64_t nb = B.bytes - skip, L = nb + tail_len;   // the stream: sorted [skip, bytes), then the tail
-  const int64_t n_win = (L + W - 1) / W;
-  uint8_t *pin[2] = {nullptr, nullptr};
-  struct PinGuard {
-    uint8_t **p;
-    ~PinGuard() {
-      for (int s = 0; s < 2; s++)
-        if (p[s]) (void)hipHostFree(p[s]);
-    }
-  } pguard{pin};
-  for (int s = 0; s < 2; s++) HIPCHK(ctx, hipHostMalloc((void **)&pin[s], (size_t)W, hipHostMallocDefault));
-  MH_TRY(ensure(ctx, B.in1, (size_t)W + 64));
-  MH_TRY(ensure(ctx, B.in2, (size_t)W + 64));
-  uint8_t *dwin[2] = {(uint8_t *)B.in1.p, (uint8_t *)B.in2.p};
-  std::mutex mu;
-  std::condition_variable cv;
-  int64_t ready = 0;            // windows assembled
-  int64_t freed = 2;            // windows whose staging slot may be refilled (slot of window i: i & 1)
-  bool stop = false;
-  std::thread asm_th([&]() {
-    for (int64_t i = 0; i < n_win; i++) {
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return stop || i < freed; });
-        if (stop) return;
-      }
-      const int64_t v0 = i * W, v1 = std::min(L, v0 + W);
-      if (std::min(v1, nb) > v0) bam_assemble(B, o, skip + v0, skip + std::min(v1, nb), pin[i & 1], 16);
-      if (v1 > nb) {
-        const int64_t t0 = std::max(v0, nb);
-        std::memcpy(pin[i & 1] + (t0 - v0), tail + (t0 - nb), (size_t)(v1 - t0));
-      }
-      std::lock_guard<std::mutex> lk(mu);
-      ready = i + 1;
-      cv.notify_all();
-    }
-  });
-  struct Join {
-    std::thread *t;
-    std::mutex *m;
-    std::condition_variable *c;
-    bool *stop;
-    ~Join() {
-      {
-        std::lock_guard<std::mutex> lk(*m);
-        *stop = true;
-        c->notify_all();
-      }
-      t->join();
-    }
-  } join{&asm_th, &mu, &cv, &stop};
-  boff->assign(1, 0);
-  int64_t zpos = 0;
-  std::vector<int64_t> bw;
-  for (int64_t i = 0; i < n_win; i++) {
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return ready > i; });
-    }
-    const int s = (int)(i & 1);
-    const int64_t len = std::min(L, (i + 1) * W) - i * W;
-    HIPCHK(ctx, hipMemcpyAsync(dwin[s], pin[s], (size_t)len, hipMemcpyHostToDevice, ctx->stream));
-    MH_TRY(slot_free(i));   // ring slot s: window i - 2's compressed pieces copied out
-    const int64_t zb = s * ring;
-    const std::function<void(int64_t, int64_t)> piece = [&](int64_t off, int64_t bytes) { on_piece(zb + off, bytes); };
-    int64_t used = 0;
-    MH_TRY(bgzf_device(ctx, ctx->stream, dwin[s], len, (uint8_t *)ctx->gz_out.p + zb, ring, &used, &bw,
-                       &piece));   // (returns with the stream drained)
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      freed = i + 3;   // slot s (its H2D is done) takes window i + 2
-      cv.notify_all();
-    }
-    boff->pop_back();
-    for (int64_t x : bw) boff->push_back(zpos + x);
-    zpos += used;
-  }
-  *nz = zpos;
-  return MH_OK;
-}
-
-// The sorted store's record stream deflated on the device and written to `path`: the header's block(s) first (hdr
-// null: none), the stream from byte `skip` followed by `tail` (tail_len bytes, host memory) cut into 0xff00-byte BGZF
-// blocks, the EOF marker when `eof`.  A writer thread copies each packed piece out (stream2, two page-locked 64 MiB
-// slots) and writes it while the next piece deflates.  boff: the data blocks' offsets from data_pos (nblocks + 1).
-struct BamPart {
-  int64_t data_pos = 0, end_pos = 0, nz = 0;
-  std::vector<int64_t> boff;
-};
-static int32_t bam_write_gpu_impl(mh_ctx *ctx, const char *path, const std::string *hdr, int64_t skip,
-                                  const uint8_t *tail, int64_t tail_len, bool eof, BamPart &P) {
-  BamStore &B = ctx->bam;
-  MH_TRY(bam_sort(ctx));
-  if (skip < 0 || skip > B.bytes || tail_len < 0 || (tail_len > 0 && !tail))
-    return arg_fail(ctx, MH_E_ARG, "BAM part: skip or tail out of range");
-  std::vector<int64_t> &boff = P.boff;
-  int64_t nz = 0;
-  struct Piece {
-    int64_t off, len;
-    hipEvent_t ev;
-  };
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<Piece> pieces;
-  bool fin = false;
-  // gz_out is sized for the whole BAM (GBs): released on every exit into the device block cache (the next job's
-  // buffers, or the next file's gz_out, take it from there)
-  struct Guard {
-    mh_ctx *c;
-    std::vector<Piece> *pc;
-    ~Guard() {
-      for (Piece &x : *pc)
-        if (x.ev) (void)hipEventDestroy(x.ev);
-      release(c->gz_out);   // (to the device block cache: the next file's output buffer)
-    }
-  } guard{ctx, &pieces};
-  MH_TRY(gz_drain(ctx));
-  const int64_t L = B.bytes - skip + tail_len;
-  // a spilled (bounded) store deflates window by window into two ring slots; otherwise one buffer for the whole file
-  const int64_t ring = B.spilled > 0 ? bgzf_device_bound(spill_window(B)) : 0;
-  MH_TRY(ensure(ctx, ctx->gz_out, (size_t)(ring ? 2 * ring : bgzf_device_bound(L))));
-  const int64_t SLOT_B = (int64_t)1 << 26;
-  for (auto &p : ctx->h_bam_pin)
-    if (!p) HIPCHK(ctx, hipHostMalloc((void **)&p, (size_t)SLOT_B, hipHostMallocDefault));
-  uint8_t *const pin[2] = {ctx->h_bam_pin[0], ctx->h_bam_pin[1]};
-  const uint8_t *z = (const uint8_t *)ctx->gz_out.p;
-  std::atomic<int> werr{(int)hipSuccess};   // (set by either thread)
-  std::string err;
-  bool wrote = false, writer_done = false;
-  size_t pieces_out = 0;   // pieces whose bytes have all been copied off the device (the ring's slots reuse them)
-  int64_t data_pos = 0, end_pos = 0;
-  const std::string no_header;
-  std::thread writer([&]() {
-    (void)hipSetDevice(ctx->device);
-    size_t item = 0;
-    int64_t in_item = 0;
-    size_t slot_piece[2] = {0, 0};   // per staging slot: 1 + the piece its sub-piece ends, or 0
-    // the next sub-piece (<= 64 MiB) of the queued pieces, waiting for the deflate to queue it
-    auto take = [&](int64_t *o, int64_t *m, hipEvent_t *ev, size_t *ends) -> bool {
-      std::unique_lock<std::mutex> lk(mu);
-      for (;;) {
-        while (item < pieces.size() && in_item >= pieces[item].len) {
-          item++;
-          in_item = 0;
-        }
-        if (item < pieces.size()) break;
-        if (fin) return false;
-        cv.wait(lk);
-      }
-      const Piece &p = pieces[item];
-      *o = p.off + in_item;
-      *m = std::min(SLOT_B, p.len - in_item);
-      *ev = p.ev;
-      in_item += *m;
-      *ends = in_item >= p.len ? item + 1 : 0;
-      return true;
-    };
-    auto issue = [&](int s, int64_t *len) -> bool {   // a copy into slot s on stream2, behind its piece's pack
-      int64_t o, m;
-      hipEvent_t ev;
-      if (!take(&o, &m, &ev, &slot_piece[s])) return false;
-      hipError_t e = hipStreamWaitEvent(ctx->stream2, ev, 0);
-      if (e == hipSuccess) e = hipMemcpyAsync(pin[s], z + o, (size_t)m, hipMemcpyDeviceToHost, ctx->stream2);
-      if (e != hipSuccess) {
-        werr = (int)e;
-        return false;
-      }
-      *len = m;
-      return true;
-    };
-    int cur = 0;
-    int64_t len_cur = 0, len_next = 0;
-    bool have = issue(0, &len_cur);
-    auto next = [&](const uint8_t **buf, int64_t *len) -> bool {
-      if (!have || werr.load() != (int)hipSuccess) return false;
-      hipError_t e = hipStreamSynchronize(ctx->stream2);   // slot cur is in (and nothing else is in flight)
-      if (e != hipSuccess) {
-        werr = (int)e;
-        return false;
-      }
-      const int s = cur;
-      if (slot_piece[s]) {   // that piece's last bytes are off the device: its ring space may be refilled
-        std::lock_guard<std::mutex> lk(mu);
-        pieces_out = std::max(pieces_out, slot_piece[s]);
-        cv.notify_all();
-      }
-      *buf = pin[s];
-      *len = len_cur;
-      have = issue(s ^ 1, &len_next);   // the following sub-piece into the other slot, while this one is written
-      len_cur = len_next;
-      cur = s ^ 1;
-      return true;
-    };
-    wrote = bgzf_write_stream(path, hdr ? *hdr : no_header, 6, next, &data_pos, &end_pos, err, eof);
-    if (!wrote) {   // drain what is in flight before the slots go
-      (void)hipStreamSynchronize(ctx->stream2);
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    writer_done = true;
-    cv.notify_all();
-  });
-  const std::function<void(int64_t, int64_t)> on_piece = [&](int64_t off, int64_t bytes) {
-    hipEvent_t ev = nullptr;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventRecord(ev, ctx->stream) != hipSuccess) {
-      if (ev) (void)hipEventDestroy(ev);
-      ev = nullptr;
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    pieces.push_back(Piece{off, ev ? bytes : 0, ev});
-    if (!ev) werr = (int)hipErrorUnknown;
-    cv.notify_all();
-  };
-  std::vector<size_t> win_end;   // win_end[i]: pieces queued before window i
-  const std::function<int32_t(int64_t)> slot_free = [&](int64_t i) -> int32_t {
-    std::unique_lock<std::mutex> lk(mu);
-    win_end.push_back(pieces.size());
-    if (i < 2) return MH_OK;
-    const size_t need = win_end[(size_t)i - 1];   // every piece of windows <= i - 2
-    cv.wait(lk, [&] { return pieces_out >= need || writer_done || werr.load() != (int)hipSuccess; });
-    if (pieces_out < need) return arg_fail(ctx, MH_E_STATE, "BAM writer stopped before the deflate ring drained");
-    return MH_OK;
-  };
-  int32_t rc = MH_OK;
-  if (B.spilled > 0) {
-    rc = bam_deflate_spilled(ctx, ring, skip, tail, tail_len, &nz, &boff, on_piece, slot_free);
-  } else {
-    // the tail after the sorted records (srecs keeps its bytes), then one deflate of [skip, bytes + tail_len)
-    if (tail_len > 0) {
-      rc = ensure_keep(ctx, B.srecs, (size_t)(B.bytes + tail_len + 64), (size_t)B.bytes);
-      if (rc == MH_OK &&
-          hipMemcpyAsync((uint8_t *)B.srecs.p + B.bytes, tail, (size_t)tail_len, hipMemcpyHostToDevice, ctx->stream) !=
-              hipSuccess)
-        rc = hip_fail(ctx, hipGetLastError(), "BAM part tail H2D", __FILE__, __LINE__);
-    }
-    if (rc == MH_OK)
-      rc = bgzf_device(ctx, ctx->stream, (const uint8_t *)B.srecs.p + skip, L, (uint8_t *)ctx->gz_out.p,
-                       (int64_t)ctx->gz_out.cap, &nz, &boff, &on_piece);
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    fin = true;
-    cv.notify_all();
-  }
-  writer.join();
-  if (rc != MH_OK) return rc;
-  if (werr.load() != (int)hipSuccess) return hip_fail(ctx, (hipError_t)werr.load(), "BAM D2H", __FILE__, __LINE__);
-  if (!wrote) return arg_fail(ctx, MH_E_ARG, err);
-  if (end_pos - data_pos != nz) return arg_fail(ctx, MH_E_STATE, "BAM: compressed bytes written differ (internal)");
-  P.data_pos = data_pos;
-  P.end_pos = end_pos;
-  P.nz = nz;
   return MH_OK;
 }
 
@@ -2274,35 +1993,7 @@ int32_t mh_bam_write_gpu(mh_ctx *ctx, const char *bam_path, const char *header_t
   BamStore &B = ctx->bam;
   if (!bam_path || (header_len > 0 && !header_text)) return arg_fail(ctx, MH_E_ARG, "null argument");
   if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
-  MH_TRY(bam_sort(ctx));
-  const int64_t n = B.n_rec;
-  // the BAI's per-record half on the device (chunks and linear windows; only their offsets cross PCIe)
-  BaiPlan plan;
-  std::vector<int64_t> offs;
-  bool dev_plan = false;
-  if (bai_path) MH_TRY(bam_bai_plan(ctx, plan, offs, &dev_plan));
-  const std::string hdr = bam_header_bytes(std::string(header_text ? header_text : "", (size_t)header_len),
-                                           B.ref_names, B.ref_len);
-  BamPart P;
-  MH_TRY(bam_write_gpu_impl(ctx, bam_path, &hdr, 0, nullptr, 0, true, P));
-  std::vector<int64_t> coff(P.boff.size());
-  for (size_t b = 0; b < P.boff.size(); b++) coff[b] = P.data_pos + P.boff[b];
-  std::string err;
-  if (bai_path) {
-    if (dev_plan) {
-      if (!bai_emit(bai_path, plan, offs.data(), coff, err)) return arg_fail(ctx, MH_E_ARG, err);
-    } else {   // outside the device plan's checks: the host plan (and its errors)
-      std::vector<int64_t> soff((size_t)n + 1, 0);
-      std::vector<BaiRec> info((size_t)n + 1);
-      MH_TRY(bam_fetch_sorted(ctx, nullptr, soff.data(), (int32_t *)info.data()));
-      if (!bai_write(bai_path, (int32_t)B.ref_names.size(), n, info.data(), soff.data(), coff, err))
-        return arg_fail(ctx, MH_E_ARG, err);
-    }
-  }
-  if (out_records) *out_records = n;
-  if (out_bytes) *out_bytes = B.bytes;
-  if (out_file_bytes) *out_file_bytes = P.end_pos + 28;
-  return MH_OK;
+  return bam_write_gpu(ctx, bam_path, header_text, header_len, bai_path, out_records, out_bytes, out_file_bytes);
 }
 
 int32_t mh_bam_write_part(mh_ctx *ctx, const char *path, const char *header_text, int64_t header_len, int64_t skip,
@@ -2313,20 +2004,8 @@ int32_t mh_bam_write_part(mh_ctx *ctx, const char *path, const char *header_text
   if (!path || !out_blocks || !out_data_pos || !out_bytes || (header_len > 0 && !header_text))
     return arg_fail(ctx, MH_E_ARG, "null argument");
   if (!B.refs_set) return arg_fail(ctx, MH_E_STATE, "call mh_bam_set_refs first");
-  std::string hdr;
-  if (header_len >= 0)
-    hdr = bam_header_bytes(std::string(header_text ? header_text : "", (size_t)header_len), B.ref_names, B.ref_len);
-  BamPart P;
-  MH_TRY(bam_write_gpu_impl(ctx, path, header_len >= 0 ? &hdr : nullptr, skip, tail, tail_len, eof != 0, P));
-  const int64_t nb = (int64_t)P.boff.size() - 1;
-  *out_blocks = nb;
-  *out_data_pos = P.data_pos;
-  *out_bytes = P.end_pos + (eof ? 28 : 0);
-  if (boff) {
-    if (boff_cap < nb + 1) return arg_fail(ctx, MH_E_CAPACITY, "block offset array too small");
-    std::memcpy(boff, P.boff.data(), 8 * (size_t)(nb + 1));
-  }
-  return MH_OK;
+  return bam_write_part(ctx, path, header_text, header_len, skip, tail, tail_len, eof, out_blocks, out_data_pos, out_bytes,
+                        boff, boff_cap);
 }
 
 int32_t mh_bam_partition(mh_ctx *ctx, const uint64_t *splitters, int32_t n_dest, uint64_t tie_base, int64_t *seg_off,

@@ -103,6 +103,17 @@ static bool compress_blocks(const uint8_t *data, int64_t n, int level, int threa
   return true;
 }
 
+bool bgzf_header_blocks(const std::string &header, int level, std::string &out) {
+  out.clear();
+  std::string blk;
+  for (size_t h = 0; h < header.size(); h += BGZF_BLOCK) {
+    const int64_t m = std::min<int64_t>(BGZF_BLOCK, (int64_t)(header.size() - h));
+    if (!bgzf_block((const uint8_t *)header.data() + h, m, level, blk)) return false;
+    out += blk;
+  }
+  return true;
+}
+
 bool bgzf_write(const char *path, const std::string &header, const uint8_t *data, int64_t n, int level, int threads,
                 std::vector<int64_t> &coff, std::string &err) {
   FILE *fp = fopen(path, "wb");
@@ -110,15 +121,9 @@ bool bgzf_write(const char *path, const std::string &header, const uint8_t *data
     err = std::string("cannot open ") + path;
     return false;
   }
-  int64_t pos = 0;
-  bool ok = true;
-  std::string blk;
-  for (size_t h = 0; h < header.size() && ok; h += BGZF_BLOCK) {
-    const int64_t m = std::min<int64_t>(BGZF_BLOCK, (int64_t)(header.size() - h));
-    ok = bgzf_block((const uint8_t *)header.data() + h, m, level, blk) && fwrite(blk.data(), 1, blk.size(), fp) ==
-         blk.size();
-    pos += (int64_t)blk.size();
-  }
+  std::string hz;
+  bool ok = bgzf_header_blocks(header, level, hz) && fwrite(hz.data(), 1, hz.size(), fp) == hz.size();
+  int64_t pos = (int64_t)hz.size();
   const int64_t nblk = (n + BGZF_BLOCK - 1) / BGZF_BLOCK;
   coff.assign(nblk + 1, 0);
   ok = ok && compress_blocks(data, n, level, threads, [&](int64_t b, const std::string &z) {
@@ -130,69 +135,6 @@ bool bgzf_write(const char *path, const std::string &header, const uint8_t *data
   ok = ok && fwrite(BGZF_EOF, 1, 28, fp) == 28;
   ok = (fclose(fp) == 0) && ok;
   if (!ok) err = std::string("BGZF write failed: ") + path;
-  return ok;
-}
-
-bool bgzf_write_blocks(const char *path, const std::string &header, int level, int64_t n_z,
-                       const std::vector<int64_t> &boff,
-                       const std::function<const uint8_t *(int64_t, int64_t)> &fetch, std::vector<int64_t> &coff,
-                       std::string &err) {
-  FILE *fp = fopen(path, "wb");
-  if (!fp) {
-    err = std::string("cannot open ") + path;
-    return false;
-  }
-  int64_t pos = 0;
-  bool ok = true;
-  std::string blk;
-  for (size_t h = 0; h < header.size() && ok; h += BGZF_BLOCK) {
-    const int64_t m = std::min<int64_t>(BGZF_BLOCK, (int64_t)(header.size() - h));
-    ok = bgzf_block((const uint8_t *)header.data() + h, m, level, blk) && fwrite(blk.data(), 1, blk.size(), fp) ==
-         blk.size();
-    pos += (int64_t)blk.size();
-  }
-  coff.resize(boff.size());
-  for (size_t b = 0; b < boff.size(); b++) coff[b] = pos + boff[b];
-  const int64_t piece = (int64_t)1 << 26;
-  for (int64_t o = 0; o < n_z && ok; o += piece) {
-    const int64_t m = std::min(piece, n_z - o);
-    const uint8_t *buf = fetch(o, m);
-    ok = buf && fwrite(buf, 1, (size_t)m, fp) == (size_t)m;
-  }
-  ok = ok && fwrite(BGZF_EOF, 1, 28, fp) == 28;
-  ok = (fclose(fp) == 0) && ok;
-  if (!ok && err.empty()) err = std::string("BGZF write failed: ") + path;
-  return ok;
-}
-
-bool bgzf_write_stream(const char *path, const std::string &header, int level,
-                       const std::function<bool(const uint8_t **, int64_t *)> &next, int64_t *data_pos,
-                       int64_t *end_pos, std::string &err, bool eof) {
-  FILE *fp = fopen(path, "wb");
-  if (!fp) {
-    err = std::string("cannot open ") + path;
-    return false;
-  }
-  int64_t pos = 0;
-  bool ok = true;
-  std::string blk;
-  for (size_t h = 0; h < header.size() && ok; h += BGZF_BLOCK) {
-    const int64_t m = std::min<int64_t>(BGZF_BLOCK, (int64_t)(header.size() - h));
-    ok = bgzf_block((const uint8_t *)header.data() + h, m, level, blk) && fwrite(blk.data(), 1, blk.size(), fp) ==
-         blk.size();
-    pos += (int64_t)blk.size();
-  }
-  *data_pos = pos;
-  const uint8_t *buf = nullptr;
-  int64_t len = 0;
-  while (ok && next(&buf, &len)) {
-    ok = fwrite(buf, 1, (size_t)len, fp) == (size_t)len;
-    pos += len;
-  }
-  *end_pos = pos;
-  ok = ok && (!eof || fwrite(BGZF_EOF, 1, 28, fp) == 28);
-  ok = (fclose(fp) == 0) && ok;
-  if (!ok && err.empty()) err = std::string("BGZF write failed: ") + path;
   return ok;
 }
 

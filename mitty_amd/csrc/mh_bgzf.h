@@ -5,7 +5,6 @@
 #pragma once
 
 #include <cstdint>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -28,22 +27,9 @@ std::string bam_header_bytes(const std::string &text, const std::vector<std::str
 bool bgzf_write(const char *path, const std::string &header, const uint8_t *data, int64_t n, int level, int threads,
                 std::vector<int64_t> &rec_block_coff, std::string &err);
 
-// The same file from data blocks deflated elsewhere (the device, mh_bam_write_gpu): `header` deflated here at `level`
-// in its own block(s), then n_z bytes of ready BGZF blocks fetched in pieces, then the EOF
-// marker.  boff[b] = offset of data block b inside those bytes (b = 0..nblocks); rec_block_coff as bgzf_write's.
-// fetch(offset, len) returns host bytes [offset, offset + len) (len <= 64 MiB), valid until the next call, or null.
-bool bgzf_write_blocks(const char *path, const std::string &header, int level, int64_t n_z,
-                       const std::vector<int64_t> &boff,
-                       const std::function<const uint8_t *(int64_t, int64_t)> &fetch,
-                       std::vector<int64_t> &rec_block_coff, std::string &err);
-
-// The same file with the data blocks handed over as they are ready: next(&buf, &len) gives the next piece of BGZF
-// bytes (false: no more).  *data_pos = the data's file offset (after the header block(s)), *end_pos = the EOF
-// marker's.
-// eof false: no EOF marker (a part of a file other writers complete, mh_bam_write_part).
-bool bgzf_write_stream(const char *path, const std::string &header, int level,
-                       const std::function<bool(const uint8_t **, int64_t *)> &next, int64_t *data_pos,
-                       int64_t *end_pos, std::string &err, bool eof = true);
+// `header` deflated at `level` into its own BGZF block(s): the head of a BAM file, whoever writes the rest (bgzf_write;
+// BgzfSink, mh_bgzfsink.hip, for blocks deflated on the device).  False when zlib fails.
+bool bgzf_header_blocks(const std::string &header, int level, std::string &out);
 
 // BAI for n sorted records whose data offsets are soff[0..n] (soff[n] = end), given the block map from bgzf_write.
 bool bai_write(const char *path, int32_t n_refs, int64_t n, const BaiRec *recs, const int64_t *soff,

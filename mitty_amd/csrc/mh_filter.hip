@@ -10,7 +10,8 @@
 //     -> k_filter_gather  a wave per 4 KiB of output, a lane per 16-byte destination word: the kept records, input
 //                         order, behind the carry of the earlier chunks
 //     -> bgzf_device      the whole 0xff00-byte blocks of [carry | kept bytes]; the rest is the next chunk's carry
-//     -> D2H into one of two page-locked buffers, written to the file while the next chunk's kernels run
+//     -> the session's BgzfSink (mh_bgzfsink.hip): its thread copies the blocks out and writes them while the next
+//                         chunk's kernels run
 //
 // The blocks are cut at fixed multiples of 0xff00 of the kept stream, so the file does not depend on how the input was
 // cut into chunks.  Once a record fails, nothing of its chunk or of a later one is written, and finish removes the file.
@@ -18,8 +19,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
 
 #include "mh_bgzf.h"
@@ -233,77 +232,33 @@ __global__ void __launch_bounds__(256) k_filter_gather(GatherArgs a) {
   }
 }
 
-using Clock = std::chrono::steady_clock;
-
-int32_t io_fail(mh_ctx *ctx, FilterState &F, const char *what) {
-  F.io_failed = true;
-  return arg_fail(ctx, MH_E_IO, std::string(what) + ": " + F.path);
+// the sink's failure as a call's result: a failed copy, or a failed write naming the path (MH_OK: neither)
+int32_t sink_failed(mh_ctx *ctx, FilterState &F) {
+  if (F.sink.hip_error() != hipSuccess) return hip_fail(ctx, F.sink.hip_error(), "filter-bam D2H", __FILE__, __LINE__);
+  if (!F.sink.failed()) return MH_OK;
+  const char *what = F.sink.close_failed ? "filter-bam: close failed: " : "filter-bam: write failed: ";
+  return arg_fail(ctx, MH_E_IO, what + F.sink.path);
 }
 
-// the file closed; removed (when it is a regular file) unless `keep`
-void close_out(FilterState &F, bool keep) {
-  if (F.fp) (void)fclose(F.fp);
-  F.fp = nullptr;
-  if (!keep && !F.path.empty()) {
-    struct stat sb;
-    if (stat(F.path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) (void)unlink(F.path.c_str());
-  }
-  F.path.clear();
-}
-
-// the compressed bytes waiting in page-locked buffer k: waited for, then written.  A failed write is kept in io_failed
-// (the chunk being queued is queued all the same; the add call and finish report it)
-int32_t flush_pin(mh_ctx *ctx, FilterState &F, int k) {
-  if (!F.pin_set[k]) return MH_OK;
-  HIPCHK(ctx, hipEventSynchronize(F.ev[k]));
-  F.pin_set[k] = false;
-  if (F.failed || F.io_failed || !F.fp) return MH_OK;
-  const Clock::time_point t0 = Clock::now();
-  const bool ok = fwrite(F.pin[k], 1, (size_t)F.pin_len[k], F.fp) == (size_t)F.pin_len[k];
-  if (ctx->timing)
-    ctx->last_times.emplace_back("filter_write", std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
-  if (!ok) F.io_failed = true;
-  return MH_OK;
-}
-
-int32_t pin_reserve(mh_ctx *ctx, FilterState &F, int k, size_t need) {
-  if (F.pin_cap[k] >= need) return MH_OK;
-  if (F.pin[k]) (void)hipHostFree(F.pin[k]);
-  F.pin[k] = nullptr;
-  F.pin_cap[k] = 0;
-  const size_t cap = need + need / 4 + 4096;
-  HIPCHK(ctx, hipHostMalloc((void **)&F.pin[k], cap, hipHostMallocDefault));
-  F.pin_cap[k] = cap;
-  return MH_OK;
-}
-
-// out[cur][0, n) (whole blocks, or the last carry) deflated and queued for the host: page-locked buffer pin_cur
+// out[cur][0, n) (whole blocks, or the last carry) deflated into z and pushed to the sink, once the sink has copied the
+// previous chunk's blocks out of z.  A failed sink takes nothing more (the add call and finish report it)
 int32_t deflate_out(mh_ctx *ctx, FilterState &F, int64_t n) {
   hipStream_t st = ctx->stream;
   int64_t used = 0;
+  if (!F.sink.wait_copied(F.sink.mark())) return MH_OK;
   MH_TRY(ensure(ctx, F.z, (size_t)bgzf_device_bound(n)));
   {
     StageScope sc(ctx, "filter_deflate");
     MH_TRY(bgzf_device(ctx, st, (const uint8_t *)F.out[F.cur].p, n, (uint8_t *)F.z.p, (int64_t)F.z.cap, &used));
   }
-  const int k = F.pin_cur;
-  MH_TRY(flush_pin(ctx, F, k));
-  MH_TRY(pin_reserve(ctx, F, k, (size_t)used));
-  {
-    StageScope sc(ctx, "filter_d2h");
-    HIPCHK(ctx, hipMemcpyAsync(F.pin[k], F.z.p, (size_t)used, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(ctx, hipEventRecord(F.ev[k], st));
-  F.pin_set[k] = true;
-  F.pin_len[k] = used;
-  F.pin_cur = k ^ 1;
+  F.sink.push(F.z.p, used, st);
   return MH_OK;
 }
 
 int32_t filter_launch(mh_ctx *ctx, const RecChunk &c) {
   FilterState &F = ctx->filter;
   hipStream_t st = ctx->stream;
-  if (F.failed || F.io_failed) return MH_OK;   // nothing of a later chunk is written
+  if (F.failed || F.sink.failed()) return MH_OK;   // nothing of a later chunk is written
   const int64_t n = c.n;
   MH_TRY(ensure(ctx, F.ksz, sizeof(uint32_t) * (size_t)n + 64));
   MH_TRY(ensure(ctx, F.klist, sizeof(int64_t) * (size_t)(2 * n + 1) + 64));
@@ -319,11 +274,8 @@ int32_t filter_launch(mh_ctx *ctx, const RecChunk &c) {
   const int64_t tiles = (n + 255) / 256;
   {
     StageScope sc(ctx, "filter_mark");
-    MarkArgs a{c.recs, c.roff, n, c.avail,
-               ScoreRule{(const char *)F.names.p, (const int32_t *)F.name_off.p, F.n_refs, (const uint8_t *)F.prefix.p,
-                         F.plen, F.max_d, F.strict},
-               F.d_lo, F.d_hi, F.mq_lo, F.mq_hi, F.keep_unscored, ksz, (unsigned long long *)F.delta.p, err,
-               c.base_rec};
+    MarkArgs a{c.recs, c.roff, n, c.avail, F.refs.rule(F.max_d, F.strict), F.d_lo, F.d_hi, F.mq_lo, F.mq_hi,
+               F.keep_unscored, ksz, (unsigned long long *)F.delta.p, err, c.base_rec};
     const int64_t grid = std::min<int64_t>(tiles, 8 * (int64_t)ctx->max_cu);
     hipLaunchKernelGGL(k_filter_mark, dim3((unsigned)grid), dim3(256), 0, st, a);
     HIPCHK(ctx, hipGetLastError());
@@ -343,8 +295,7 @@ int32_t filter_launch(mh_ctx *ctx, const RecChunk &c) {
   MH_TRY(session_commit(ctx, F.ses, F.delta, F.acc, FC_N, FC_N));
   HIPCHK(ctx, hipMemcpyAsync(F.h_rb, tot, sizeof(KB), hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipMemcpyAsync(F.h_rb + 2, err, 8, hipMemcpyDeviceToHost, st));
-  // the previous chunk's compressed bytes go to the file while the device works on this one
-  MH_TRY(flush_pin(ctx, F, F.pin_cur ^ 1));
+  // (the sink's thread writes the previous chunk's compressed bytes while the device works on this one)
   SYNCCHK(ctx, hipStreamSynchronize(st));
   if ((uint64_t)F.h_rb[2] != ~(uint64_t)0) {
     F.failed = true;
@@ -368,13 +319,13 @@ int32_t filter_launch(mh_ctx *ctx, const RecChunk &c) {
   return MH_OK;
 }
 
-// the session's device work waited for, its file closed and removed: the state a new begin starts from
+// the sink stopped, the session's unfinished file closed and removed (when it is a regular file): the state a new
+// begin starts from
 void filter_drop(FilterState &F) {
-  for (int k = 0; k < 2; k++) {
-    if (F.pin_set[k]) (void)hipEventSynchronize(F.ev[k]);
-    F.pin_set[k] = false;
-  }
-  close_out(F, false);
+  F.sink.abort();
+  struct stat sb;
+  if (F.unfinished && stat(F.sink.path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) (void)unlink(F.sink.path.c_str());
+  F.unfinished = false;
   F.ses.begun = false;
 }
 
@@ -391,23 +342,15 @@ int32_t filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64
   if (max_d < 0 || max_d > (1 << 20)) return arg_fail(ctx, MH_E_ARG, "max_d must be 0..2^20");
   if (d_lo < 0 || d_lo > d_hi || d_hi > max_d) return arg_fail(ctx, MH_E_ARG, "need 0 <= d_lo <= d_hi <= max_d");
   if (mq_lo < 0 || mq_lo > mq_hi || mq_hi > 255) return arg_fail(ctx, MH_E_ARG, "need 0 <= mq_lo <= mq_hi <= 255");
-  if (F.ses.begun || F.fp) filter_drop(F);   // a session left open: as mh_filter_abort
+  filter_drop(F);   // a session left open: as mh_filter_abort
   std::vector<std::string> ref_names;
   std::vector<int64_t> ref_len;
-  std::vector<int32_t> off(1, 0);
-  std::string cat;
   const char *p = names;
   for (int32_t i = 0; i < n_refs; i++) {
-    const size_t l = strlen(p);
-    ref_names.emplace_back(p, l);
+    ref_names.emplace_back(p);
     ref_len.push_back(lengths[i]);
-    cat.append(p, l);
-    p += l + 1;
-    off.push_back((int32_t)cat.size());
+    p += ref_names.back().size() + 1;
   }
-  const std::string pre = sample_prefix ? sample_prefix : "";
-  F.n_refs = n_refs;
-  F.plen = (int32_t)pre.size();
   F.max_d = max_d;
   F.strict = strict ? 1 : 0;
   F.d_lo = d_lo;
@@ -415,37 +358,29 @@ int32_t filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64
   F.mq_lo = mq_lo;
   F.mq_hi = mq_hi;
   F.keep_unscored = keep_unscored ? 1 : 0;
-  F.failed = F.io_failed = false;
+  F.failed = false;
   F.carry = 0;
-  F.cur = F.pin_cur = 0;
+  F.cur = 0;
   hipStream_t st = ctx->stream;
-  for (int k = 0; k < 2; k++)
-    if (!F.ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&F.ev[k], hipEventDisableTiming));
   if (!F.h_rb) HIPCHK(ctx, hipHostMalloc((void **)&F.h_rb, 64, hipHostMallocDefault));
   MH_TRY(ensure(ctx, F.acc, sizeof(uint64_t) * FC_N));
   MH_TRY(ensure(ctx, F.delta, sizeof(uint64_t) * FC_N));
   MH_TRY(ensure(ctx, F.tot, 64));
-  MH_TRY(ensure(ctx, F.names, cat.size() + 16));
-  MH_TRY(ensure(ctx, F.name_off, sizeof(int32_t) * off.size()));
-  MH_TRY(ensure(ctx, F.prefix, pre.size() + 16));
-  if (!cat.empty()) HIPCHK(ctx, hipMemcpyAsync(F.names.p, cat.data(), cat.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipMemcpyAsync(F.name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
-  if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(F.prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
+  MH_TRY(F.refs.upload(ctx, n_refs, names, sample_prefix));
   MH_TRY(session_clear(ctx, F.ses));
   HIPCHK(ctx, hipMemsetAsync(F.acc.p, 0, sizeof(uint64_t) * FC_N, st));
-  SYNCCHK(ctx, hipStreamSynchronize(st));   // (the host strings above are done with)
-  // the header, deflated here in its own block(s); the records start a fresh block behind it
-  F.path = out_path;
+  SYNCCHK(ctx, hipStreamSynchronize(st));   // (the session's cleared state is in place before a file is made)
+  // the header, deflated by the sink in its own block(s); the records start a fresh block behind it
   const std::string hdr = bam_header_bytes(std::string(header_text ? header_text : "", (size_t)header_len), ref_names,
                                            ref_len);
-  int64_t data_pos = 0, end_pos = 0;
-  std::string err;
-  const bool wrote = bgzf_write_stream(out_path, hdr, 6, [](const uint8_t **, int64_t *) { return false; }, &data_pos,
-                                       &end_pos, err, false);
-  if (wrote) F.fp = fopen(out_path, "ab");
-  if (!wrote || !F.fp) {
-    close_out(F, false);
-    return arg_fail(ctx, MH_E_IO, "filter-bam: cannot write " + std::string(out_path) + (err.empty() ? "" : ": " + err));
+  int64_t data_pos = 0;
+  F.unfinished = true;   // (a file the open created and could not write is removed as well)
+  if (!F.sink.open(ctx, out_path, &hdr, 6, &data_pos)) {
+    const int32_t rc = F.sink.hip_error() != hipSuccess
+                           ? sink_failed(ctx, F)
+                           : arg_fail(ctx, MH_E_IO, "filter-bam: cannot write " + F.sink.path + ": " + F.sink.io_error());
+    filter_drop(F);
+    return rc;
   }
   F.ses.begun = true;
   return MH_OK;
@@ -454,32 +389,24 @@ int32_t filter_begin(mh_ctx *ctx, int32_t n_refs, const char *names, const int64
 int32_t filter_add_records(mh_ctx *ctx, const uint8_t *recs, int64_t len, const int64_t *roff, int64_t n) {
   FilterState &F = ctx->filter;
   MH_TRY(session_add_records(ctx, F.ses, recs, len, roff, n, [ctx](const RecChunk &c) { return filter_launch(ctx, c); }));
-  return F.io_failed ? arg_fail(ctx, MH_E_IO, "filter-bam: write failed: " + F.path) : MH_OK;
+  return sink_failed(ctx, F);
 }
 
 int32_t filter_finish(mh_ctx *ctx, int64_t *counts) {
   FilterState &F = ctx->filter;
   MH_TRY(session_begun(ctx, F.ses));
   int32_t rc = MH_OK;
-  if (!F.failed && !F.io_failed) {
-    rc = flush_pin(ctx, F, F.pin_cur ^ 1);
-    if (rc == MH_OK && F.carry > 0) {   // the carry is the last block
-      rc = deflate_out(ctx, F, F.carry);
-      if (rc == MH_OK) rc = flush_pin(ctx, F, F.pin_cur ^ 1);
-    }
-    char eof[28];
-    (void)mh_bgzf_eof(eof);
-    if (rc == MH_OK && fwrite(eof, 1, 28, F.fp) != 28) rc = io_fail(ctx, F, "filter-bam: write failed");
-    if (rc == MH_OK) {
-      FILE *fp = F.fp;
-      F.fp = nullptr;
-      if (fclose(fp) != 0) rc = io_fail(ctx, F, "filter-bam: close failed");
+  if (!F.failed && !F.sink.failed()) {
+    if (F.carry > 0) rc = deflate_out(ctx, F, F.carry);   // the carry is the last block
+    if (rc == MH_OK && F.sink.finish(true, nullptr) && ctx->timing) {
+      ctx->last_times.emplace_back("filter_d2h", F.sink.d2h_ms);
+      ctx->last_times.emplace_back("filter_write", F.sink.write_ms);
     }
   }
   std::string failed;
   const int32_t rc_s = session_failed(ctx, F.ses, &failed);   // (waits for the stream)
   if (rc == MH_OK) rc = rc_s;
-  if (rc == MH_OK && F.io_failed) rc = arg_fail(ctx, MH_E_IO, "filter-bam: write failed: " + F.path);
+  if (rc == MH_OK) rc = sink_failed(ctx, F);
   if (rc == MH_OK && !failed.empty()) rc = arg_fail(ctx, MH_E_ARG, failed);
   if (rc == MH_OK && counts) {
     if (hipMemcpyAsync(counts, F.acc.p, sizeof(int64_t) * FC_N, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -490,7 +417,7 @@ int32_t filter_finish(mh_ctx *ctx, int64_t *counts) {
     filter_drop(F);
     return rc;
   }
-  close_out(F, true);
+  F.unfinished = false;
   F.ses.begun = false;
   return MH_OK;
 }
@@ -503,18 +430,11 @@ int32_t filter_abort(mh_ctx *ctx) {
 }
 
 void filter_release(FilterState &F) {
-  close_out(F, false);   // (a session still open when its context goes: aborted)
-  release(F.acc); release(F.delta); release(F.names); release(F.name_off); release(F.prefix);
-  release(F.ksz); release(F.klist); release(F.scan); release(F.tot); release(F.z);
-  for (int k = 0; k < 2; k++) {
-    release(F.out[k]);
-    if (F.pin[k]) (void)hipHostFree(F.pin[k]);
-    if (F.ev[k]) (void)hipEventDestroy(F.ev[k]);
-    F.pin[k] = nullptr;
-    F.pin_cap[k] = 0;
-    F.ev[k] = nullptr;
-    F.pin_set[k] = false;
-  }
+  filter_drop(F);   // (a session still open when its context goes: aborted)
+  F.sink.release();
+  release(F.acc); release(F.delta); release(F.ksz); release(F.klist); release(F.scan); release(F.tot); release(F.z);
+  F.refs.release();
+  for (DevBuf &b : F.out) release(b);
   if (F.h_rb) (void)hipHostFree(F.h_rb);
   F.h_rb = nullptr;
   session_release(F.ses);

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mitty_hip.h"
+#include "mh_piecequeue.h"
 
 namespace mh {
 
@@ -231,10 +233,10 @@ extern const RecTexts SCORE_TEXTS, MODEL_TEXTS, BQ_TEXTS, COV_TEXTS, FILTER_TEXT
 // Alignment scorer (mh_score.hip): both matrices and the counts of one scoring session, resident until read back.
 struct ScoreState {
   RecSession ses{SCORE_TEXTS};
-  int32_t max_d = 0, max_v = 0, strict = 0, n_refs = 0, plen = 0;
+  int32_t max_d = 0, max_v = 0, strict = 0;
   int64_t n_mq = 0, n_dv = 0, n_all = 0;   // u64 cells of mq_mat, d_err_mat, and both + the 4 counts
   DevBuf acc, delta;           // [mq_mat | d_err_mat | counts]: the session's sums / the chunk being scored
-  DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
+  RefNames refs;               // header names, sample prefix
 };
 
 // Read-model builder (mh_model.hip, bam2illumina): the session's histograms, resident until read back.  The `bq`
@@ -271,32 +273,67 @@ struct CovState {
   bool scanned = false;        // depth and the covered counts hold the track as it is now
 };
 
+// A BGZF file written from blocks that were deflated in HBM (mh_bgzfsink.hip).  The owner opens it with the header,
+// pushes pieces of device memory as they are packed and goes on working; the sink's thread copies each piece out on
+// ctx->stream2, behind the piece's event, through two page-locked slots, and writes one slot while the other fills.
+// The thread touches nothing of the context but what open() handed it; its errors are values the owner reads.
+struct BgzfSink {
+  static constexpr int64_t SLOT_BYTES = (int64_t)1 << 26;
+  // the file created, `header` (null: none) written in its own block(s) deflated at `level` and flushed, the thread
+  // started; *data_pos = the file offset of the first pushed byte
+  bool open(mh_ctx *ctx, const char *path, const std::string *header, int level, int64_t *data_pos);
+  void push(const void *d, int64_t bytes, hipStream_t st);   // bytes at device address d, ready behind st's work so far
+  int64_t mark() { return q.mark(); }                        // pieces pushed so far
+  bool wait_copied(int64_t mark);   // every piece before `mark` has left the device (false: the sink failed)
+  // the pushed pieces written, the EOF marker when `eof`, the file closed; *end_pos (may be null) = the marker's offset
+  bool finish(bool eof, int64_t *end_pos);
+  void abort();                     // the thread stopped and joined, the file closed as it is (the owner may remove it)
+  bool failed() const { return herr.load() != (int)hipSuccess || ioerr.load(); }
+  hipError_t hip_error() const { return (hipError_t)herr.load(); }
+  std::string io_error() const;     // "cannot open <path>", "BGZF write failed: <path>", or empty
+  void release();                   // abort, and the slots and events freed
+  std::string path;
+  bool close_failed = false;        // finish's fclose failed (the owner's message may say so)
+  double d2h_ms = 0, write_ms = 0;  // host clock, summed by the thread: waiting for its copies; in fwrite
+
+ private:
+  void run();
+  bool issue(int s, PieceQueue::Sub *sub, bool wait);
+  PieceQueue q{SLOT_BYTES};
+  FILE *fp = nullptr;
+  int64_t pos = 0;                  // bytes written
+  std::thread th;
+  int device = 0;
+  hipStream_t copy_stream = nullptr;
+  uint8_t *pin[2] = {nullptr, nullptr};       // page-locked on first use, kept until release
+  hipEvent_t ev_copy[2] = {nullptr, nullptr}; // after the copy into pin[s]
+  bool in_flight[2] = {false, false};
+  std::vector<hipEvent_t> ev_piece;           // one per piece of a file, used again by the next file
+  size_t n_piece = 0;
+  std::atomic<int> herr{(int)hipSuccess};     // (set by either thread)
+  std::atomic<bool> ioerr{false};
+  bool open_failed = false;
+};
+
 // filter-bam (mh_filter.hip): the session's rule and counts, the kept byte stream on its way into BGZF blocks, and the
 // output file.
 struct FilterState {
   RecSession ses{FILTER_TEXTS};
-  int32_t max_d = 0, strict = 0, n_refs = 0, plen = 0;
+  int32_t max_d = 0, strict = 0;
   int32_t d_lo = 0, d_hi = 0, mq_lo = 0, mq_hi = 0, keep_unscored = 0;
   DevBuf acc, delta;           // u64[8]: seen, kept, dropped by score / by MAPQ, skipped unplaced / sample, bytes in / kept
-  DevBuf names, name_off, prefix;   // header names (concatenated + offsets), sample prefix
+  RefNames refs;               // header names, sample prefix
   DevBuf ksz;                  // u32 per record of the chunk: its kept bytes (0: dropped)
   DevBuf klist;                // i64: destination offsets of the kept records (+ the total), then their source offsets
   DevBuf scan, tot;            // the scan's look-back scratch; its totals (kept bytes, kept records)
   DevBuf out[2];               // [carry | the chunk's kept bytes]: the chunk being gathered / the next one's carry
-  DevBuf z;                    // the chunk's BGZF blocks
+  DevBuf z;                    // the chunk's BGZF blocks, pushed to the sink (copied out before the next chunk's)
   int cur = 0;                 // out[cur] holds the carry
   int64_t carry = 0;           // kept bytes not yet in a block (< 0xff00)
-  uint8_t *pin[2] = {nullptr, nullptr};   // page-locked: a chunk's blocks on their way to the file
-  size_t pin_cap[2] = {0, 0};
-  int64_t pin_len[2] = {0, 0};
-  hipEvent_t ev[2] = {nullptr, nullptr};  // after the copy into pin[k]
-  bool pin_set[2] = {false, false};       // pin[k] holds bytes not yet written
-  int pin_cur = 0;             // the buffer the next chunk's blocks go to
   int64_t *h_rb = nullptr;     // page-locked: the chunk's totals and the error word
-  FILE *fp = nullptr;
-  std::string path;
+  BgzfSink sink;               // the output file
+  bool unfinished = false;     // sink.path is this session's file, not finished: dropping the session removes it
   bool failed = false;         // a record failed: nothing more is written
-  bool io_failed = false;      // a write failed
 };
 
 struct StageTime {
@@ -471,8 +508,8 @@ struct mh_ctx {
   mh::DevBuf cr_rows, cr_codes;
   mh::DevBuf scan_partials_w;            // look-back scratch of the writer stream's scans
   int64_t *h_small = nullptr;            // pinned 4 KiB for small readbacks (no staged copy per value)
-  uint8_t *h_bam_pin[2] = {nullptr, nullptr};   // mh_bam_write_gpu's two 64 MiB D2H slots (kept: page-locking
-                                                // 128 MiB per BAM file cost ~13 ms)
+  mh::BgzfSink bam_sink;                 // mh_bam_write_gpu / _part's file (kept: page-locking its two 64 MiB slots
+                                         // cost ~13 ms per BAM file)
 
   // timing
   bool timing = false;
@@ -607,6 +644,8 @@ int32_t bgzf_device(mh_ctx *ctx, hipStream_t st, const uint8_t *d_in, int64_t n,
                     // d_out (+ the end), for a BAI; on_piece(offset, bytes): a piece of d_out is queued on `st` (the
                     // caller may copy it out behind that point while the next piece deflates)
 int64_t bgzf_device_bound(int64_t n);
+// copies that mh_output_bgzf_pair left in flight out of gz_out's halves: done before anything else rewrites gz_out
+int32_t gz_drain(mh_ctx *ctx);
 int gpu_numa_node(int dev);   // the NUMA node of the device's PCI function (sysfs), -1 when unknown
 std::mutex &host_allocs_mu();  // mh_host_alloc's node-bound registrations (address -> bytes)
 std::unordered_map<void *, size_t> &host_allocs();
@@ -653,6 +692,13 @@ struct BaiPlan;
 // compact array of the data offsets they need.  *ok = false (and MH_OK) when the records are outside what the
 // device plan checks (a record past its reference's length, an unsorted store): the caller then plans on the host.
 int32_t bam_bai_plan(mh_ctx *ctx, BaiPlan &plan, std::vector<int64_t> &offs, bool *ok);
+// The sorted store deflated on the device and written as a BAM (and its BAI) / as a part of one (mh_bamwrite.hip):
+// mh_bam_write_gpu's and mh_bam_write_part's bodies, behind their argument checks
+int32_t bam_write_gpu(mh_ctx *ctx, const char *bam_path, const char *header_text, int64_t header_len,
+                      const char *bai_path, int64_t *out_records, int64_t *out_bytes, int64_t *out_file_bytes);
+int32_t bam_write_part(mh_ctx *ctx, const char *path, const char *header_text, int64_t header_len, int64_t skip,
+                       const uint8_t *tail, int64_t tail_len, int32_t eof, int64_t *out_blocks, int64_t *out_data_pos,
+                       int64_t *out_bytes, int64_t *boff, int64_t boff_cap);
 void bam_release(BamStore &B);
 void bam_free_spill(BamStore &B);
 int32_t newline_index(mh_ctx *ctx, const uint8_t *b, int64_t len, DevBuf &nl, int64_t *count);

@@ -43,6 +43,18 @@ struct RecChunk {
 };
 using RecLaunch = std::function<int32_t(const RecChunk &)>;   // the consumer's kernels over a chunk, on ctx->stream
 
+// What the sessions that score records (mh_score.hip, mh_filter.hip) keep of the header on the device: the reference
+// names, concatenated with their offsets, and the sample prefix
+struct ScoreRule;   // mh_scorerec.h, where rule() is defined
+struct RefNames {
+  DevBuf names, name_off, prefix;
+  int32_t n_refs = 0, plen = 0;
+  // names: n_refs strings, each ending in NUL; sample_prefix may be null.  Returns with the copies done
+  int32_t upload(mh_ctx *ctx, int32_t n_refs, const char *names, const char *sample_prefix);
+  ScoreRule rule(int32_t max_d, int32_t strict) const;
+  void release();
+};
+
 int32_t session_begun(mh_ctx *ctx, const RecSession &S);   // MH_E_STATE with the session's text when it is not
 // the chunks in flight done, no failing record, no records counted; queued on ctx->stream (the caller synchronises)
 int32_t session_clear(mh_ctx *ctx, RecSession &S);

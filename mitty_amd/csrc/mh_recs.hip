@@ -160,4 +160,34 @@ void session_release(RecSession &S) {
   S.begun = false;
 }
 
+int32_t RefNames::upload(mh_ctx *ctx, int32_t n, const char *ref_names, const char *sample_prefix) {
+  std::vector<int32_t> off(1, 0);
+  std::string cat;
+  const char *p = ref_names;
+  for (int32_t i = 0; i < n; i++) {
+    const size_t l = strlen(p);
+    cat.append(p, l);
+    p += l + 1;
+    off.push_back((int32_t)cat.size());
+  }
+  const std::string pre = sample_prefix ? sample_prefix : "";
+  n_refs = n;
+  plen = (int32_t)pre.size();
+  hipStream_t st = ctx->stream;
+  MH_TRY(ensure(ctx, names, cat.size() + 16));
+  MH_TRY(ensure(ctx, name_off, sizeof(int32_t) * off.size()));
+  MH_TRY(ensure(ctx, prefix, pre.size() + 16));
+  if (!cat.empty()) HIPCHK(ctx, hipMemcpyAsync(names.p, cat.data(), cat.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
+  if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
+  SYNCCHK(ctx, hipStreamSynchronize(st));   // (the host strings above are done with)
+  return MH_OK;
+}
+
+void RefNames::release() {
+  mh::release(names);
+  mh::release(name_off);
+  mh::release(prefix);
+}
+
 }  // namespace mh

@@ -154,12 +154,14 @@ int32_t score_launch(mh_ctx *ctx, const RecChunk &c) {
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipMemsetAsync(S.delta.p, 0, sizeof(uint64_t) * S.n_all, st));
   unsigned long long *d = (unsigned long long *)S.delta.p;
-  const DevBuf &names = c.store ? c.store->names : S.names, &name_off = c.store ? c.store->name_off : S.name_off;
-  ScoreArgs a{c.recs, c.roff, c.n, c.avail,
-              ScoreRule{(const char *)names.p, (const int32_t *)name_off.p,
-                        c.store ? (int32_t)c.store->ref_names.size() : S.n_refs, (const uint8_t *)S.prefix.p, S.plen,
-                        S.max_d, S.strict},
-              S.max_d, S.max_v, d, d + S.n_mq, d + S.n_mq + S.n_dv, (unsigned long long *)S.ses.err.p, c.base_rec};
+  ScoreRule rule = S.refs.rule(S.max_d, S.strict);
+  if (c.store) {
+    rule.names = (const char *)c.store->names.p;
+    rule.name_off = (const int32_t *)c.store->name_off.p;
+    rule.n_refs = (int32_t)c.store->ref_names.size();
+  }
+  ScoreArgs a{c.recs, c.roff, c.n, c.avail, rule, S.max_d, S.max_v, d, d + S.n_mq, d + S.n_mq + S.n_dv,
+              (unsigned long long *)S.ses.err.p, c.base_rec};
   // a workgroup's LDS counters are 32-bit: at most 4096 tiles (2^20 records, < 2^8 list items each) per workgroup
   const int64_t tiles = (c.n + 255) / 256;
   const int64_t grid = std::min<int64_t>(tiles, std::max<int64_t>(8 * (int64_t)ctx->max_cu, (tiles + 4095) / 4096));
@@ -194,28 +196,10 @@ int32_t score_begin(mh_ctx *ctx, int32_t n_refs, const char *names, int32_t max_
   S.n_mq = 100 * ncol;
   S.n_dv = (2 * (int64_t)max_v_len + 2) * ncol;
   S.n_all = S.n_mq + S.n_dv + 4;
-  std::vector<int32_t> off(1, 0);
-  std::string cat;
-  const char *p = names;
-  for (int32_t i = 0; i < n_refs; i++) {
-    const size_t l = strlen(p);
-    cat.append(p, l);
-    p += l + 1;
-    off.push_back((int32_t)cat.size());
-  }
-  const std::string pre = sample_prefix ? sample_prefix : "";
-  S.n_refs = n_refs;
-  S.plen = (int32_t)pre.size();
-  hipStream_t st = ctx->stream;
   MH_TRY(ensure(ctx, S.acc, sizeof(uint64_t) * S.n_all));
   MH_TRY(ensure(ctx, S.delta, sizeof(uint64_t) * S.n_all));
-  MH_TRY(ensure(ctx, S.names, cat.size() + 16));
-  MH_TRY(ensure(ctx, S.name_off, sizeof(int32_t) * off.size()));
-  MH_TRY(ensure(ctx, S.prefix, pre.size() + 16));
-  if (!cat.empty()) HIPCHK(ctx, hipMemcpyAsync(S.names.p, cat.data(), cat.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipMemcpyAsync(S.name_off.p, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice, st));
-  if (!pre.empty()) HIPCHK(ctx, hipMemcpyAsync(S.prefix.p, pre.data(), pre.size(), hipMemcpyHostToDevice, st));
-  MH_TRY(score_clear(ctx));   // (synchronises: the host strings above are done with)
+  MH_TRY(S.refs.upload(ctx, n_refs, names, sample_prefix));
+  MH_TRY(score_clear(ctx));
   S.ses.begun = true;
   return MH_OK;
 }
@@ -250,7 +234,8 @@ int32_t score_reset(mh_ctx *ctx) {
 }
 
 void score_release(ScoreState &S) {
-  release(S.acc); release(S.delta); release(S.names); release(S.name_off); release(S.prefix);
+  release(S.acc); release(S.delta);
+  S.refs.release();
   session_release(S.ses);
 }
 

@@ -26,6 +26,10 @@ struct ScoreRule {
   int32_t plen;
   int32_t max_d, strict;
 };
+inline ScoreRule RefNames::rule(int32_t max_d, int32_t strict) const {
+  return ScoreRule{(const char *)names.p, (const int32_t *)name_off.p, n_refs, (const uint8_t *)prefix.p, plen, max_d,
+                   strict};
+}
 
 // A record's verdict.  kind != 0: the record fails the session (SE_*).  Otherwise skip_tid / skip_smp: not scored
 // (tid < 0; the sample prefix differs), or scored: d_err in [-max_d, max_d], and the scored group's v_list at

@@ -378,7 +378,51 @@ def test_abort_removes_the_file_and_a_path_that_cannot_be_made_is_an_oserror(ctx
   assert 'call mh_filter_begin first' in str(e.value)
 
 
-# ---- 8. the command -------------------------------------------------------------------------------------------------
+# ---- 8. two device-BGZF files open on one context ---------------------------------------------------------------------
+def test_a_bam_written_from_the_store_between_two_adds(native, tmp_path):
+  """The filter's file and the god-aligner store's file (mh_bam_write_gpu) go through a sink each, on the same context
+  and the same copy stream: the store is built and written between the session's second and third add.  Both files
+  are byte-equal to what each operation writes alone on a fresh context."""
+  from tests import bam_cases as C
+  c = C.case('ties')
+  header = '@HD\tVN:1.0\tSO:coordinate\n'
+  recs = [(wrong(i, pad=i % 23) if i % 2 else right(i, pad=i % 5))[1] for i in range(300)]
+  calls = [recs[0:100], recs[100:200], recs[200:300]]
+
+  def store_bam(ctx, path):
+    ctx.bam_set_refs(list(c.ref_names), list(c.ref_lengths))
+    ctx.bam_add_fastq(c.fq1, c.fq2)
+    ctx.bam_write_gpu(path, header, bai_path=path + '.bai')
+    return _read(path), _read(path + '.bai')
+
+  def filtered(ctx, path, between=None):
+    ctx.filter_begin([s['SN'] for s in SQ], [s['LN'] for s in SQ], TEXT, path)
+    for k, part in enumerate(calls):
+      if k == 2 and between:
+        between()
+      ctx.filter_add_records(b''.join(part), SU.offsets(part))
+    assert ctx.filter_finish()['kept'] == 150
+    return _read(path)
+
+  alone = []
+  for what in (store_bam, filtered):
+    fresh = native.Context(0)
+    try:
+      alone.append(what(fresh, str(tmp_path / 'alone_{}.bam'.format(len(alone)))))
+    finally:
+      fresh.close()
+  both = native.Context(0)
+  try:
+    got = []
+    data = filtered(both, str(tmp_path / 'f.bam'), lambda: got.append(store_bam(both, str(tmp_path / 's.bam'))))
+  finally:
+    both.close()
+  assert got[0] == alone[0]
+  assert data == alone[1]
+  assert len(FR.split_bam(data)[2]) == 150 and len(alone[0][0]) > 28
+
+
+# ---- 9. the command -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('gpu_inflate', [False, True])
 def test_cli(native, golden_bam, tmp_path, gpu_inflate):
   from click.testing import CliRunner

@@ -298,6 +298,35 @@ def test_host_cpp_under_asan_ubsan(tmp_path):
   assert r.stdout.count(b'\n') >= len(cmds)
 
 
+@pytest.mark.parametrize('sanitizer', ['address,undefined', 'thread'])
+def test_piece_queue_under_sanitizers(tmp_path, sanitizer):
+  """The queue between the device deflate and the thread that copies its output to a file (mh_piecequeue.h), alone, with
+  64-byte slots and a producer and a consumer thread (tests/sanitize/san_piecequeue.cpp): the cut into sub-pieces, empty
+  pieces, the two-windows-in-flight rule of the spilled store's ring, close on an empty queue, a consumer that stops."""
+  import shutil
+  import subprocess
+  if shutil.which('g++') is None:
+    pytest.skip('no g++')
+  exe = str(tmp_path / 'san_piecequeue')
+  # the sanitizer's runtime linked statically: the program needs nothing of the environment it is started in
+  flags = ['-fsanitize=' + sanitizer] + (['-static-libtsan'] if sanitizer == 'thread' else
+                                         ['-static-libasan', '-static-libubsan', '-fno-sanitize-recover=undefined'])
+  if sanitizer == 'thread':   # libtsan is not on every machine: probed with a program that cannot fail to compile
+    probe = tmp_path / 'probe.cpp'
+    probe.write_text('int main() { return 0; }\n')
+    if subprocess.run(['g++'] + flags + [str(probe), '-o', str(tmp_path / 'probe')], stdout=subprocess.DEVNULL,
+                      stderr=subprocess.DEVNULL).returncode != 0:
+      pytest.skip('g++ does not link libtsan here')
+  build = subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer'] + flags +
+                         [os.path.join(REPO, 'tests', 'sanitize', 'san_piecequeue.cpp'), '-lpthread', '-o', exe],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+  assert build.returncode == 0, build.stdout.decode(errors='replace')[-4000:]
+  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
+  r = subprocess.run(['timeout', '120', exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+  err = r.stderr.decode(errors='replace')
+  assert r.returncode == 0 and r.stdout == b'ok\n' and 'Sanitizer' not in err and 'runtime error' not in err, err[-4000:]
+
+
 @pytest.mark.parametrize('out_name', ['out.vcf', 'out.vcf.gz'])
 def test_filter_variants_matches_reference(tmp_path, out_name):
   """filter-variants (vcfio.prepare_variant_file, vcfio.py:129-168) keeps exactly the records the reference writes
